@@ -23,11 +23,21 @@ One STEP = one batch of B=256 queries through the whole path:
 Inputs (the query batch and term ids, both indexes) are resident before the
 timed region; every stage runs in full inside every timed step.
 
-The JSON line also carries, measured in the same run:
+A plain run sets up, warms up, times the K steps, writes the last step's
+outputs if --dump-outputs DIR is given (DIR/scores.npy, DIR/ids.npy) and
+prints the line: value, ms_per_step and what the timed steps themselves
+recorded (roofline: the scans' HIP-event times and clock, the faithful band).
+At N > 1 over RCCL the native_exchange leg below runs too, because a
+validated one supplies `value`.
+
+With --full the JSON line also carries, measured in the same run:
+  checks           the last timed step's top-10 = the planted docs, sorted,
+                   oracle MaxSim of the final candidates of a few queries;
   bf16             (fp32 main) the same K steps + p50 on a bf16 index of the
                    same corpus (the faithful index's hi tokens, no copy);
                    `--dtype bf16` swaps the two (main bf16, side leg "faithful");
-  roofline.band_ms the faithful band work per step (HIP events, timed region);
+  collectives      (N > 1) per-step collective times, 2 instrumented steps;
+  configs_4_5      (8 ranks, or --c45 on) BASELINE configs 4 and 5;
   native_exchange  (N > 1, RCCL) the same K steps with the exchange inside the
                    C ABI (cbv2_search_sharded_* / cbv2_rerank_sharded);
   cpu_baseline     (N = 1 only; null at N > 1) the CPU restatements timed on
@@ -41,7 +51,7 @@ rank that fails one records the error in the line with every other rank.
 N>1: the SAME 1M-doc corpus is split into N contiguous shards, one per rank
 (strong scaling); value = B*K / max-over-ranks wall time.
 
-Run:  python bench.py [--gpus N --steps K --warmup W] [--dtype fp32|bf16|fp8]
+Run:  python bench.py [--gpus N --steps K --warmup W] [--dtype fp32|bf16|fp8] [--full] [--dump-outputs DIR]
       torchrun --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
 """
 from __future__ import annotations
@@ -189,6 +199,17 @@ def timed_steps(run_steps, K, W, world, on_start=None):
         dist.all_reduce(e, op=dist.ReduceOp.MAX)
         elapsed = float(e.item())
     return outs, elapsed
+
+
+def dump_outputs(path, scores, ids):
+    """--dump-outputs: what the caller of the timed path receives from its last
+    timed step, one array per file: ``scores.npy`` [B, final_k] float32 (the
+    rerank scores, best first) and ``ids.npy`` [B, final_k] float64 (the
+    global doc ids, exact in float64).  The inputs are seeded, so two builds
+    run with the same arguments can be compared file for file."""
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "scores.npy"), scores.detach().cpu().numpy().astype(np.float32))
+    np.save(os.path.join(path, "ids.npy"), ids.detach().cpu().numpy().astype(np.float64))
 
 
 def clock_view(flop_per_launch, avg_ms, peak_tflops, clock_ghz, nominal_ghz=NOMINAL_GHZ):
@@ -372,6 +393,13 @@ def main():
     ap.add_argument("--k", type=int, default=100)
     ap.add_argument("--fused", type=int, default=50)
     ap.add_argument("--final-k", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything else the line can carry: the output checks "
+                         "(planted top-10, oracle spot parity), the B=1 latency, the side leg, the CPU baseline, "
+                         "the per-step collective times and the config-4/5 legs.  Off: the line carries only "
+                         "what the timed steps themselves measured")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs to DIR/scores.npy and DIR/ids.npy (rank 0)")
     ap.add_argument("--p50-iters", type=int, default=100)
     ap.add_argument("--cpu-budget", type=float, default=12.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -395,6 +423,8 @@ def main():
                          "within 1e-4 -- bf16 hi scanned + residual-certified band, DESIGN §3.7), bf16 tokens, "
                          "or MXFP8 e4m3 + E8M0 (config 5)")
     args = ap.parse_args()
+    if args.c45 == "on" and not args.full:
+        ap.error("--c45 on is one of the extra legs: it needs --full")
     # stdout carries exactly the ONE JSON line: everything else any layer prints
     # to fd 1 (Python, RCCL / gloo C++ logging) is sent to stderr from here on
     global JSON_FD
@@ -522,35 +552,44 @@ def main():
         bs = ix.last_band.float()
         band = {"batch": B, "mean": round(float(bs.mean()), 1), "max": int(bs.max()),
                 "overflow_rows": int((bs < 0).sum())}
+    fs, fi = outs[-1]                    # the last timed step's (scores, ids): what a caller receives
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, fs, fi)
+    fi_h = fi.cpu().numpy()
+
+    # Everything from here to the line measures or checks something beside the
+    # headline and runs only with --full (the N > 1 native-exchange leg is the
+    # exception: a validated one supplies the headline itself, see main_line)
+    full = args.full
     coll = {}
-    if world > 1:                        # per-step collective times: 2 untimed steps, instrumented
+    if full and world > 1:               # per-step collective times: 2 untimed steps, instrumented
         searcher.time_collectives(True)
         stepper(searcher, Q)(2)
         torch.cuda.synchronize()
         coll = {k: {f: v / 2 for f, v in d.items()} for k, d in searcher.collective_times().items()}
 
     # ---- correctness of the timed output (size-independent properties)
-    fs, fi = outs[-1]
-    fi_h = fi.cpu().numpy()
-    top10_planted = planted_frac(fi_h)
-    sorted_ok = bool((torch.diff(fs, dim=1) <= 0).all().item())
+    top10_planted = planted_frac(fi_h) if full else None
+    sorted_ok = bool((torch.diff(fs, dim=1) <= 0).all().item()) if full else None
 
     # ---- p50 / p99 latency at batch 1 (whole hot path, one query).  One shard
     # (or the native exchange): the one-round-trip path (cbv2_retrieve_begin /
     # _finish: stages 2 -> host RRF -> 3 in C++, one host round trip); the
     # torch.distributed exchange at N > 1: the stages one by one (`step`)
-    one = one_trip(searcher)
-    one_same = same_as_step(searcher, one, Q1) if one is not None else None
-    _, p50_step, _ = latency(searcher, Q1) if one is not None else (None, None, None)
-    lat, p50, p99 = latency(searcher, Q1, one)
-    latency_path = ("one host round trip (cbv2_retrieve_begin/_finish_host; the call returns with the top-10 "
-                    "on the host)" if one is not None
-                    else "stages one by one (torch.distributed exchange)")
-    bm_ms = []
-    for _ in range(3):                                  # stage 1 alone (host), for the record
-        t = time.perf_counter()
-        bm_all()
-        bm_ms.append((time.perf_counter() - t) * 1e3)
+    one = one_same = p50_step = p50 = p99 = latency_path = None
+    lat, bm_ms = [], []
+    if full:
+        one = one_trip(searcher)
+        one_same = same_as_step(searcher, one, Q1) if one is not None else None
+        _, p50_step, _ = latency(searcher, Q1) if one is not None else (None, None, None)
+        lat, p50, p99 = latency(searcher, Q1, one)
+        latency_path = ("one host round trip (cbv2_retrieve_begin/_finish_host; the call returns with the top-10 "
+                        "on the host)" if one is not None
+                        else "stages one by one (torch.distributed exchange)")
+        for _ in range(3):                              # stage 1 alone (host), for the record
+            t = time.perf_counter()
+            bm_all()
+            bm_ms.append((time.perf_counter() - t) * 1e3)
 
     # ---- dominant kernel: the MaxSim scan launches of the timed region above
     # (fp32-faithful: the bf16 scan of hi, the same kernel and template)
@@ -601,17 +640,19 @@ def main():
 
     # ---- spot parity: oracle MaxSim of the final candidates, on the owning rank
     check_rows = list(range(min(args.check_queries, B)))
-    if fp8:                              # the oracle scores the same dequantized fp8 values
+    bad = tol = None
+    if full and fp8:                     # the oracle scores the same dequantized fp8 values
         from oracle import oracle as orc
         qq, qs = quantize_mxfp8(Q)
         Qd = orc.mxfp8_dequant(qq.cpu().numpy(), qs.cpu().numpy())
         docs_fn = lambda sel: orc.mxfp8_dequant(ix.tokens[sel].cpu().numpy(), ix.scales[sel].cpu().numpy())  # noqa: E731
         tol = 2e-3
-    else:                                # fp32: the fp32 values themselves; bf16: the stored bf16 values
+    elif full:                           # fp32: the fp32 values themselves; bf16: the stored bf16 values
         Qd = Q.float().cpu().numpy()
         docs_fn = lambda sel: tokens[sel].float().cpu().numpy()   # noqa: E731
         tol = 1e-4 if faithful else 1e-3
-    bad = spot_check(fs, fi_h, Qd, docs_fn, begin, end, check_rows, tol, world, dev)
+    if full:
+        bad = spot_check(fs, fi_h, Qd, docs_fn, begin, end, check_rows, tol, world, dev)
 
     # ---- N > 1 over RCCL: the same K steps with the native (in-ABI) exchange
     native = None
@@ -644,7 +685,7 @@ def main():
     # ---- CPU baseline: N = 1 only (the contract times it once, on the host of
     # the one-GPU run; an N > 1 line carries null and the ranks do not idle)
     cpu = None
-    if world == 1 and not args.no_cpu_baseline:
+    if full and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(Q, tokens, n_total, args.cpu_budget)
     if world > 1:
         dist.barrier()
@@ -655,7 +696,7 @@ def main():
     #                holds; no copy), scores within 1e-3 of the bf16 values;
     #   bf16 main -> "faithful": the fp32-faithful index of the same corpus.
     side = None
-    if not args.no_side_leg and args.dtype in ("fp32", "bf16"):
+    if full and not args.no_side_leg and args.dtype in ("fp32", "bf16"):
         side_name = "bf16" if faithful else "faithful"
 
         def side_prepare():
@@ -712,7 +753,8 @@ def main():
     # ---- BASELINE configs 4 and 5 on the node (8 ranks): the 10M-doc corpus
     # sharded over the ranks, stage 2 (scan + top-100 + ONE all-gather + merge)
     c45 = None
-    if args.c45 == "on" or (args.c45 == "auto" and world == 8 and args.dtype in ("fp32", "bf16") and not replicas):
+    if full and (args.c45 == "on" or (args.c45 == "auto" and world == 8 and args.dtype in ("fp32", "bf16")
+                                      and not replicas)):
         one = searcher = ix = tokens = None   # noqa: F841  free HBM for the 10M-doc shards
         torch.cuda.synchronize()
         torch.cuda.empty_cache()
@@ -763,7 +805,7 @@ def main():
             "torch_exchange": ({k: (round(v, 3) if isinstance(v, float) and k.startswith("p") else v)
                                 for k, v in torch_leg.items()} if torch_leg is not None else None),
             "one_trip_equals_stages": one_same,
-            "host_bm25_ms_per_batch": round(min(bm_ms), 3),
+            "host_bm25_ms_per_batch": round(min(bm_ms), 3) if bm_ms else None,
             "roofline": {"bound": "mfma", "kernel": want, "variant": variant, "achieved": round(achieved, 2),
                          "peak": peak, "unit": "TFLOP/s", "frac": round(achieved / peak, 4),
                          "traffic": traffic, "traffic_source": traffic_src, "avg_ms": round(scan_avg, 3),
@@ -783,7 +825,8 @@ def main():
                          "pmc_reference": pmc_ref},
             "cpu_baseline": cpu,
             "checks": {"top10_equals_planted": top10_planted, "sorted": sorted_ok, "oracle_mismatch_queries": bad,
-                       "oracle_checked_queries": len(check_rows), "oracle_tolerance": tol},
+                       "oracle_checked_queries": len(check_rows), "oracle_tolerance": tol} if full else None,
+            "full": full,
         }
         if band is not None:
             line["faithful_band"] = band

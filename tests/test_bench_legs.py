@@ -104,6 +104,23 @@ def test_main_line_takes_native_numbers_once_validated():
     assert line["value"] == 1000.0 and torch_leg is None and line["exchange"].startswith("native")
 
 
+def test_dump_outputs_writes_float_arrays(tmp_path):
+    """bench.dump_outputs (--dump-outputs DIR): the last timed step's scores as
+    float32 and its ids as float64 (exact for int32 ids), one .npy each, into a
+    directory it creates."""
+    import numpy as np
+
+    import bench
+    scores = torch.tensor([[0.75, 0.5], [0.25, 0.125]])
+    ids = torch.tensor([[2**31 - 1, 7], [999_999, 0]], dtype=torch.int32)
+    out = tmp_path / "a" / "b"
+    bench.dump_outputs(str(out), scores, ids)
+    assert sorted(p.name for p in out.iterdir()) == ["ids.npy", "scores.npy"]
+    s, i = np.load(out / "scores.npy"), np.load(out / "ids.npy")
+    assert s.dtype == np.float32 and np.array_equal(s, scores.numpy())
+    assert i.dtype == np.float64 and np.array_equal(i, ids.numpy().astype(np.float64))
+
+
 def test_clock_view_reproduces_avg_ms():
     """bench.clock_view: the line's roofline frac split into THIS run's held
     clock (the scans' in-kernel probe) and the MFMA-busy fraction at that

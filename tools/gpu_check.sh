@@ -21,10 +21,10 @@ if [ "$P" = A ]; then
   tail -n 2 "$O/gputest.log"
   timeout -k 10 300 python3 -c "import __graft_entry__ as g; g.smoke()" > "$O/smoke.log" 2>&1
   echo smoke-ok
-  timeout -k 10 600 python3 -u bench.py > "$O/bench.json" 2> "$O/bench.err"
+  timeout -k 10 600 python3 -u bench.py --full > "$O/bench.json" 2> "$O/bench.err"
   cat "$O/bench.json"
   timeout -k 10 600 rocprofv3 --kernel-trace --stats -f csv -d "$O/bench_trace" -o bench -- \
-    python3 bench.py > "$O/bench_traced.json" 2> "$O/bench_traced.err"
+    python3 bench.py --full > "$O/bench_traced.json" 2> "$O/bench_traced.err"
   python3 tools/kernel_table.py "$(find "$O/bench_trace" -name '*kernel_trace.csv' -print -quit)" 3 \
     > "$O/bench_kernel_table.txt"
   cp "$(find "$O/bench_trace" -name '*kernel_stats.csv' -print -quit)" "$O/bench_kernel_stats.csv"
@@ -39,6 +39,6 @@ else
   done
   timeout -k 10 600 python3 tools/config_sweep.py --out "$O/config_sweep.jsonl" > "$O/config_sweep.log" 2>&1
   cat "$O/config_sweep.jsonl"
-  timeout -k 10 600 python3 -u bench.py --dtype fp8 > "$O/bench_fp8.json" 2> "$O/bench_fp8.err"
+  timeout -k 10 600 python3 -u bench.py --full --dtype fp8 > "$O/bench_fp8.json" 2> "$O/bench_fp8.err"
   cat "$O/bench_fp8.json"
 fi

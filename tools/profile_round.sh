@@ -20,10 +20,10 @@ export TMPDIR=/tmp
 cp "$ROOT/profiles/pmc_scan.json" "$OUT/pmc_scan.json"
 if [ -z "$SKIP_TRACE" ]; then
   timeout -k 10 300 rocprofv3 --kernel-trace --stats -f csv -d "$OUT/bench" -o bench -- \
-    python3 "$ROOT/bench.py" --steps 5 --warmup 2 --p50-iters 10 --no-cpu-baseline --no-faithful \
+    python3 "$ROOT/bench.py" --full --steps 5 --warmup 2 --p50-iters 10 --no-cpu-baseline --no-faithful \
     > "$OUT/bench.json" 2> "$OUT/bench.err"
   timeout -k 10 300 rocprofv3 --kernel-trace --stats -f csv -d "$OUT/bench_fp8" -o bench -- \
-    python3 "$ROOT/bench.py" --dtype fp8 --steps 5 --warmup 2 --p50-iters 10 --no-cpu-baseline \
+    python3 "$ROOT/bench.py" --full --dtype fp8 --steps 5 --warmup 2 --p50-iters 10 --no-cpu-baseline \
     > "$OUT/bench_fp8.json" 2> "$OUT/bench_fp8.err"
   echo trace-done
 fi
