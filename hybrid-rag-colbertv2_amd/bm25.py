@@ -187,13 +187,41 @@ class NativeBM25:
         except Exception:
             pass
 
-    def search(self, q_terms: np.ndarray, q_offsets: np.ndarray, k: int, n_threads: int = 0):
-        """Queries as CSR of term ids -> (global ids int32 [B, k], scores float32 [B, k])."""
+    def _allow_words(self, allow) -> Optional[np.ndarray]:
+        """A filter as the host bitmap cbv2_bm25_search_filtered takes: uint32
+        words (bit i & 31 of word i >> 5 = LOCAL doc i), from packed words or a
+        bool mask [n_docs] (numpy or CPU / device torch)."""
+        if allow is None:
+            return None
+        if hasattr(allow, "detach"):
+            allow = allow.detach().cpu().numpy()
+        a = np.asarray(allow)
+        nw = (self.n_docs + 31) // 32
+        if a.dtype == np.bool_:
+            if a.shape != (self.n_docs,):
+                raise ValueError(f"an allow mask must be bool [{self.n_docs}]")
+            bits = np.zeros(nw * 32, np.uint8)
+            bits[: self.n_docs] = a
+            return np.ascontiguousarray(np.packbits(bits, bitorder="little").view(np.uint32))
+        if a.dtype not in (np.uint32, np.int32) or a.shape != (nw,):
+            raise ValueError(f"allow must be a bool mask [{self.n_docs}] or uint32 words [{nw}]")
+        return np.ascontiguousarray(a.view(np.uint32))
+
+    def search(self, q_terms: np.ndarray, q_offsets: np.ndarray, k: int, n_threads: int = 0, allow=None):
+        """Queries as CSR of term ids -> (global ids int32 [B, k], scores float32 [B, k]).
+        ``allow`` (a bool mask over the local docs, or its packed uint32 words):
+        only those docs are ranked and padded with (cbv2_bm25_search_filtered)."""
         q_terms = np.ascontiguousarray(q_terms, np.int32)
         q_offsets = np.ascontiguousarray(q_offsets, np.int64)
         B = len(q_offsets) - 1
         ids = np.empty((B, k), np.int32)
         sc = np.empty((B, k), np.float32)
+        words = self._allow_words(allow)
+        if words is not None:
+            _lib.check(_lib.lib().cbv2_bm25_search_filtered(
+                self._h, q_terms.ctypes.data if q_terms.size else None, q_offsets.ctypes.data, B, int(k),
+                int(n_threads), words.ctypes.data if words.size else None, ids.ctypes.data, sc.ctypes.data))
+            return ids, sc
         _lib.check(_lib.lib().cbv2_bm25_search(self._h, q_terms.ctypes.data if q_terms.size else None,
                                                q_offsets.ctypes.data, B, int(k), int(n_threads),
                                                ids.ctypes.data, sc.ctypes.data))
@@ -275,13 +303,14 @@ class HostBM25:
         self.n_docs = len(rows)
         self._native = NativeBM25(*self._corpus, len(self.vocab), self.k1, self.b)
 
-    def retrieve(self, query_tokens, k: int = 10, n_threads: int = 0):
+    def retrieve(self, query_tokens, k: int = 10, n_threads: int = 0, allow=None):
         """-> (doc ids int64 [n_queries, k], scores float32 [n_queries, k]); rows with no
-        scoring term pad with the lowest-id zero-score docs (then -1 past the corpus)."""
+        scoring term pad with the lowest-id zero-score docs (then -1 past the corpus).
+        ``allow``: rank (and pad with) only these docs (see ``NativeBM25.search``)."""
         if self._native is None:
             raise RuntimeError("BM25 index not built: call index() or load() first")
         q, off = to_csr([self._ids(t, grow=False) for t in self._rows(query_tokens)])
-        ids, sc = self._native.search(q, off, k, n_threads)
+        ids, sc = self._native.search(q, off, k, n_threads, allow=allow)
         return ids.astype(np.int64), sc
 
     # ---------------------------------------------------------------- persistence

@@ -930,14 +930,18 @@ __device__ __forceinline__ void clock_probe(uint64_t* p, bool end) {
 
 template <int WAVES, int QW, int D = 2, int NBUF = 3, bool STAMPS = false, int TPI = 32, int OCC = 2,
           bool SPREAD = false, int FK = 0, bool SPLITLOAD = false, bool ARRIVE = false, int PROBE = 0, int LD = kLd,
-          int MORDER = 0, int AUX = 0, bool BMK = false>
+          int MORDER = 0, int AUX = 0, bool BMK = false, bool IDX = false>
 __global__ __launch_bounds__(WAVES * 64, OCC) void maxsim_scan16x4_kernel(
     const uint8_t* __restrict__ tokens, const int32_t* __restrict__ doclens, int64_t n,
     const uint16_t* __restrict__ Q, int B, int lq, float* __restrict__ out, int64_t ld_out,
     int64_t chunk_docs, int64_t static_docs, int* __restrict__ task_ctr, int task_docs,
     uint64_t* __restrict__ stamps, int topk_k = 0, uint64_t* __restrict__ part = nullptr, int nslots = 0,
     int tail_slices = 1, uint32_t* __restrict__ bmk = nullptr, int64_t bmk_ld = 0, uint32_t* __restrict__ sbk = nullptr,
-    int64_t sbk_ld = 0) {
+    int64_t sbk_ld = 0, const int32_t* __restrict__ ids = nullptr) {
+  // IDX (the filtered search's subset scan): the n "docs" are the entries of
+  // an ascending list of local doc ids; entry i is doc ids[i] (its tokens and
+  // its length go through the list) and scores into column i of the compact
+  // row.  A piece's 4 rows lie in one doc, so the list index is wave-uniform.
   // TPI tokens of 4 docs per iteration (32: 32 KiB, 64: 64 KiB), IPG per group
   constexpr int QPB = WAVES * QW;
   constexpr int kIterBytes = 4 * TPI * kRowBytes;
@@ -1053,7 +1057,9 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void maxsim_scan16x4_kernel(
     const uint32_t poff = piece_src(jj, pdoc);
     int d = 4 * G + pdoc;
     d = d < rnd ? d : rnd - 1;  // the last group's missing docs: any valid doc (rows masked)
-    const uint8_t* src = tokens + (size_t)(rb + d) * kDocStride + (size_t)j * TPI * kRowBytes + poff;
+    size_t di = (size_t)(rb + d);
+    if constexpr (IDX) di = (size_t)ids[rb + __builtin_amdgcn_readfirstlane(d)];
+    const uint8_t* src = tokens + di * kDocStride + (size_t)j * TPI * kRowBytes + poff;
     __builtin_amdgcn_global_load_lds((gbl_void_t*)src, (lds_void_t*)(smem + buf * kIterBytes + piece * 1024), 16, 0,
                                      AUX);
   };
@@ -1172,7 +1178,7 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void maxsim_scan16x4_kernel(
           int dl4[4];
 #pragma unroll
           for (int x = 0; x < 4; ++x) {
-            const int v = (4 * G + x < nd) ? doclens[d_begin + 4 * G + x] : 0;
+            const int v = (4 * G + x < nd) ? doclens[IDX ? (int64_t)ids[d_begin + 4 * G + x] : d_begin + 4 * G + x] : 0;
             dl4[x] = v < 0 ? 0 : (v > LD ? LD : v);
           }
           dl_min = min(min(dl4[0], dl4[1]), min(dl4[2], dl4[3]));
@@ -1469,11 +1475,18 @@ __device__ __forceinline__ int sload_len(const int32_t* p) {
 // one store per block, and the separate block-max launch is skipped.
 // PF (lab): the next tile's fragments are read from the ring while this
 // tile's MFMAs run (the LDS read latency off the critical path).
-template <int QW, int AUX, int WAVES = 4, int SLOTS = kStreamSlots, bool TW2 = false, bool PF = false>
+// IDX (the filtered search's subset scan): the n "docs" are the entries of an
+// ascending list of local doc ids -- entry i is doc ids[i], whose length and
+// base address go through the list (two dependent scalar loads per doc, off
+// the vmcnt count like the lengths), and its score lands in column i of the
+// compact row.  Only the listed docs' token tiles are streamed.
+template <int QW, int AUX, int WAVES = 4, int SLOTS = kStreamSlots, bool TW2 = false, bool PF = false,
+          bool IDX = false>
 __global__ __launch_bounds__(WAVES * 64, 1) void maxsim_scan_stream_kernel(
     const uint8_t* __restrict__ tokens, const int32_t* __restrict__ doclens, int64_t n,
     const uint16_t* __restrict__ Q, int B, int lq, float* __restrict__ out, int64_t ld_out, int64_t chunk_docs,
-    int ld, uint32_t* __restrict__ bm, int64_t bm_ld, uint32_t* __restrict__ sb, int64_t sb_ld) {
+    int ld, uint32_t* __restrict__ bm, int64_t bm_ld, uint32_t* __restrict__ sb, int64_t sb_ld,
+    const int32_t* __restrict__ ids = nullptr) {
   __shared__ __attribute__((aligned(1024))) uint8_t smem[WAVES * SLOTS * 4096];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -1488,13 +1501,20 @@ __global__ __launch_bounds__(WAVES * 64, 1) void maxsim_scan_stream_kernel(
   const int nd = (int)(d_end - d_begin);
   uint8_t* ring = smem + wave * (SLOTS * 4096);
   const size_t doc_bytes = (size_t)ld * kRowBytes;
-  const int32_t* dls = doclens + d_begin;
+  const int32_t* dls = IDX ? ids + d_begin : doclens + d_begin;   // IDX: the list entries of this range
+  int iid = 0;   // IDX: the doc id of the issue cursor's entry
   // 32-bit cursor arithmetic keeps every comparison on the scalar unit (a
   // 64-bit compare goes to the VALU, the loop turns "divergent" and hipcc
   // loads the lengths through the vector path, whose vmcnt(0) would drain
   // the ring at every doc)
   auto ntiles = [&](int d) -> int {
-    int dl = sload_len(dls + d);
+    int dl;
+    if constexpr (IDX) {
+      iid = sload_len(dls + d);
+      dl = sload_len(doclens + iid);
+    } else {
+      dl = sload_len(dls + d);
+    }
     dl = dl < 0 ? 0 : (dl > ld ? ld : dl);
     return (dl + 15) >> 4;
   };
@@ -1512,10 +1532,10 @@ __global__ __launch_bounds__(WAVES * 64, 1) void maxsim_scan_stream_kernel(
   int itile = 0, intl = ntiles(0);
   while (intl == 0 && ++idoc < nd) intl = ntiles(idoc);
   int issued = 0;
-  const uint8_t* tbase = tokens + (size_t)d_begin * doc_bytes;
+  const uint8_t* tbase = IDX ? tokens : tokens + (size_t)d_begin * doc_bytes;
   auto issue_next = [&]() {
     if (idoc >= nd) return;
-    const uint8_t* base = tbase + (size_t)idoc * doc_bytes + (size_t)itile * 16 * kRowBytes;
+    const uint8_t* base = tbase + (size_t)(IDX ? iid : idoc) * doc_bytes + (size_t)itile * 16 * kRowBytes;
     uint8_t* dst = ring + (issued & (SLOTS - 1)) * 4096;
 #pragma unroll
     for (int q = 0; q < 4; ++q)
@@ -1558,7 +1578,7 @@ __global__ __launch_bounds__(WAVES * 64, 1) void maxsim_scan_stream_kernel(
     issue_next();
   }
   for (int i = 0; i < nd; ++i) {
-    int dl = sload_len(dls + i);
+    int dl = IDX ? sload_len(doclens + sload_len(dls + i)) : sload_len(dls + i);
     dl = dl < 0 ? 0 : (dl > ld ? ld : dl);
     const int nt = (dl + 15) >> 4;
     float m[QW][2];
@@ -5751,6 +5771,17 @@ struct cbv2_index {
   size_t band_ev_used = 0;
   bool band_open = false;
   std::vector<hipEvent_t> band_ev;
+  int filter_path = 0;   // CBV2_OPT_FILTER_PATH (0: automatic, 1: subset where supported, 2: dense)
+};
+
+// A doc filter (cbv2_filter_create): the ascending list of the allowed local
+// doc ids, compacted from the caller's bitmap into the caller's buffer.
+// Read-only after creation; bound to the index's n, id_base and device.
+struct cbv2_filter {
+  int device = 0;
+  int64_t n = 0, id_base = 0;
+  int64_t m = 0;                 // allowed docs
+  const int32_t* ids = nullptr;  // [m] ascending local ids (head of the caller's buffer)
 };
 
 namespace {
@@ -7040,6 +7071,217 @@ int launch_rescore(cbv2_index* ix, const F32Ws* w, int B, int lq, const int32_t*
                      only_neg, (int)ix->ld, pw, lb_min);
   return launch_check("rescore_x3_kernel");
 }
+
+// ---------------------------------------------------------------------------
+// Filtered search (cbv2_filter_*, cbv2_search_filtered).
+// Compaction of the allow bitmap into the ascending id list, three launches:
+// the popcount of each workgroup's kFltWords words, an exclusive prefix sum
+// over the workgroup counts (one workgroup, a running carry), and the scatter
+// (a workgroup-level prefix over its words' popcounts, each thread then writes
+// its word's set bits in ascending order).  Bits at positions >= n never count.
+// ---------------------------------------------------------------------------
+constexpr int kFltWords = 256;   // bitmap words per compaction workgroup (8192 docs), one per thread
+
+__device__ __forceinline__ uint32_t filter_word(const uint32_t* __restrict__ allow, int64_t w, int64_t n) {
+  const int64_t nw = (n + 31) >> 5;
+  if (w >= nw) return 0u;
+  uint32_t v = allow[w];
+  if (w == nw - 1 && (n & 31) != 0) v &= (1u << (n & 31)) - 1u;
+  return v;
+}
+
+// inclusive prefix sum of one int per thread over a 256-thread workgroup
+__device__ __forceinline__ int block_scan256(int v, int* s) {
+  s[threadIdx.x] = v;
+  __syncthreads();
+  for (int d = 1; d < 256; d <<= 1) {
+    const int t = (int)threadIdx.x >= d ? s[threadIdx.x - d] : 0;
+    __syncthreads();
+    s[threadIdx.x] += t;
+    __syncthreads();
+  }
+  return s[threadIdx.x];
+}
+
+__global__ __launch_bounds__(kFltWords) void filter_count_kernel(const uint32_t* __restrict__ allow, int64_t n,
+                                                                 int32_t* __restrict__ blk) {
+  __shared__ int s[256];
+  const int c = __popc(filter_word(allow, (int64_t)blockIdx.x * kFltWords + threadIdx.x, n));
+  const int incl = block_scan256(c, s);
+  if (threadIdx.x == 255) blk[blockIdx.x] = incl;
+}
+
+__global__ __launch_bounds__(256) void filter_offsets_kernel(const int32_t* __restrict__ blk, int64_t nblk,
+                                                             int32_t* __restrict__ off, int32_t* __restrict__ total) {
+  __shared__ int s[256];
+  __shared__ int carry;
+  if (threadIdx.x == 0) carry = 0;
+  __syncthreads();
+  for (int64_t base = 0; base < nblk; base += 256) {   // block-uniform
+    const int64_t i = base + threadIdx.x;
+    const int v = i < nblk ? blk[i] : 0;
+    const int incl = block_scan256(v, s);
+    const int c = carry;
+    if (i < nblk) off[i] = c + incl - v;
+    __syncthreads();
+    if (threadIdx.x == 255) carry = c + incl;
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) *total = carry;
+}
+
+__global__ __launch_bounds__(kFltWords) void filter_scatter_kernel(const uint32_t* __restrict__ allow, int64_t n,
+                                                                   const int32_t* __restrict__ off,
+                                                                   int32_t* __restrict__ ids) {
+  __shared__ int s[256];
+  const int64_t w = (int64_t)blockIdx.x * kFltWords + threadIdx.x;
+  uint32_t v = filter_word(allow, w, n);
+  const int c = __popc(v);
+  int64_t pos = (int64_t)off[blockIdx.x] + block_scan256(c, s) - c;
+  while (v != 0u) {
+    const int b = __ffs((int)v) - 1;
+    if (pos < n) ids[pos] = (int32_t)(w * 32 + b);   // (pos < n always, unless the bitmap changed under the launches)
+    ++pos;
+    v &= v - 1u;
+  }
+}
+
+// The dense path's column gather: row[b][p] = dense[b][ids[p]].
+__global__ __launch_bounds__(256) void filter_gather_kernel(const float* __restrict__ dense, int64_t ld,
+                                                            const int32_t* __restrict__ ids, int64_t m, int B,
+                                                            float* __restrict__ row) {
+  for (int b = blockIdx.y; b < B; b += gridDim.y)
+    for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < m; p += (int64_t)gridDim.x * blockDim.x)
+      row[(size_t)b * m + p] = dense[(size_t)b * ld + ids[p]];
+}
+
+// Row positions of the compact row's top-k -> global ids (id_base + ids[pos];
+// the list is ascending, so position order is id order); padding stays -1.
+__global__ __launch_bounds__(256) void filter_map_ids_kernel(int32_t* __restrict__ out_i, int64_t total,
+                                                             const int32_t* __restrict__ ids, int64_t m,
+                                                             int64_t id_base) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= total) return;
+  const int32_t p = out_i[i];
+  out_i[i] = (p >= 0 && p < m) ? (int32_t)(id_base + ids[p]) : -1;
+}
+
+size_t filter_buf_layout(int64_t n, size_t* off_blk, size_t* off_off, size_t* off_total) {
+  auto r256 = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const int64_t nn = n > 0 ? n : 1;
+  const int64_t nblk = ((nn + 31) / 32 + kFltWords - 1) / kFltWords;
+  size_t off = r256((size_t)nn * sizeof(int32_t));   // the id list (m <= n)
+  if (off_blk) *off_blk = off;
+  off += r256((size_t)nblk * sizeof(int32_t));
+  if (off_off) *off_off = off;
+  off += r256((size_t)nblk * sizeof(int32_t));
+  if (off_total) *off_total = off;
+  return off + 256;
+}
+
+// The subset scans of a bf16 index (ld = 128): the production kernels with the
+// id-list indirection (IDX), static split only, compact row out [B][m].
+template <int QW>
+int launch_stream_ids(cbv2_index* ix, const cbv2_filter* f, const uint16_t* Q, int B, int lq, float* out,
+                      hipStream_t st) {
+  const int64_t m = f->m;
+  const int nq_groups = (B + QW - 1) / QW;
+  const int64_t target_waves = 4LL * cu_count(ix->device) * kDirectOversub;
+  int64_t n_chunks = target_waves / nq_groups;
+  if (n_chunks > m) n_chunks = m;
+  if (n_chunks < 1) n_chunks = 1;
+  const int64_t chunk_docs = (m + n_chunks - 1) / n_chunks;
+  n_chunks = (m + chunk_docs - 1) / chunk_docs;
+  const int64_t grid = ((int64_t)nq_groups * n_chunks + 3) / 4;
+  if (grid > 0x7fffffff) return fail(CBV2_EUNSUPPORTED, "scan grid too large");
+  hipLaunchKernelGGL((maxsim_scan_stream_kernel<QW, 2, 4, kStreamSlots, false, false, true>), dim3((unsigned)grid),
+                     dim3(256), 0, st, ix->tokens, ix->doclens, m, Q, B, lq, out, m, chunk_docs, (int)ix->ld,
+                     (uint32_t*)nullptr, (int64_t)0, (uint32_t*)nullptr, (int64_t)0, f->ids);
+  return launch_check("maxsim_scan_stream_kernel (subset)");
+}
+
+template <int WAVES, int QW, int PER_CU, int TPI = 32, bool SPLITLOAD = false>
+int launch_scan16x4_ids(cbv2_index* ix, const cbv2_filter* f, const uint16_t* Q, int B, int lq, float* out,
+                        hipStream_t st) {
+  constexpr int QPB = WAVES * QW;
+  const int64_t m = f->m;
+  const int nq_groups = (B + QPB - 1) / QPB;
+  int64_t n_chunks = (int64_t)PER_CU * cu_count(ix->device) / nq_groups;   // never more workgroups than resident slots
+  if (n_chunks > m) n_chunks = m;
+  if (n_chunks < 1) n_chunks = 1;
+  const int64_t chunk_docs = (m + n_chunks - 1) / n_chunks;
+  n_chunks = (m + chunk_docs - 1) / chunk_docs;
+  if ((int64_t)nq_groups * n_chunks > 0x7fffffff) return fail(CBV2_EUNSUPPORTED, "scan grid too large");
+  hipLaunchKernelGGL((maxsim_scan16x4_kernel<WAVES, QW, 2, 2, false, TPI, 2, false, 0, SPLITLOAD, false, 0, kLd, 0, 0,
+                                             false, true>),
+                     dim3((unsigned)(nq_groups * n_chunks)), dim3(WAVES * 64), 0, st, ix->tokens, ix->doclens, m, Q, B,
+                     lq, out, m, chunk_docs, /*static_docs=*/m, (int*)nullptr, 0, (uint64_t*)nullptr, 0,
+                     (uint64_t*)nullptr, 0, 1, (uint32_t*)nullptr, (int64_t)0, (uint32_t*)nullptr, (int64_t)0, f->ids);
+  return launch_check("maxsim_scan16x4_kernel (subset)");
+}
+
+int scan_maxsim_subset(cbv2_index* ix, const cbv2_filter* f, const uint16_t* Q, int B, int lq, float* out,
+                       hipStream_t st) {
+  if (B <= kDirectMaxB)   // HBM-bound: only the listed docs' token tiles move
+    return B == 1 ? launch_stream_ids<1>(ix, f, Q, B, lq, out, st) : launch_stream_ids<2>(ix, f, Q, B, lq, out, st);
+  switch (pick_shape(kBf16Shapes, B)) {   // each listed doc is loaded once per query group
+    case kScan16x4W4Q1: return launch_scan16x4_ids<4, 1, 2>(ix, f, Q, B, lq, out, st);
+    case kScan16x4W4Q2: return launch_scan16x4_ids<4, 2, 2>(ix, f, Q, B, lq, out, st);
+    case kScan16x4W4: return launch_scan16x4_ids<4, 4, 2>(ix, f, Q, B, lq, out, st);
+    default: return launch_scan16x4_ids<8, 4, 1, 64, true>(ix, f, Q, B, lq, out, st);
+  }
+}
+
+// The faithful subset: cbv2_score_f32's arithmetic (one (query, doc) pair per
+// workgroup, all three products in the kernel) over the id list -- the same
+// list for every row (ld_c = 0), local ids (id_base 0).
+int rescore_subset(cbv2_index* ix, const cbv2_filter* f, const F32Ws* w, int B, int lq, float* out, hipStream_t st) {
+  const int64_t grid_auto = std::min<int64_t>(kRsSplitGrid, std::max<int64_t>(256, 4096 / std::max(B, 1)));
+  const int64_t grid_max = ix->rescore_grid > 0 ? ix->rescore_grid : grid_auto;
+  const unsigned gx = (unsigned)(f->m < grid_max ? f->m : grid_max);   // a row's pairs beyond the grid stride it
+  const bool two = (int64_t)gx * B > 3LL * cu_count(ix->device);
+  auto kern = two ? rescore_split_kernel<false, 2> : rescore_split_kernel<false, 4>;
+  hipLaunchKernelGGL(kern, dim3(gx, (unsigned)B), dim3(two ? 128 : 256), 0, st, ix->tokens, ix->resid, ix->doclens,
+                     ix->n, (int64_t)0, w->qhi, w->qlo, lq, f->ids, (const int32_t*)nullptr, f->m, (int64_t)0, out,
+                     f->m, (const int32_t*)nullptr, (int)ix->ld, (uint32_t*)nullptr, (int64_t)0, (float*)nullptr,
+                     (int32_t*)nullptr, 0, (float*)nullptr, (int32_t*)nullptr, RowSelect(), TaggedCand());
+  return launch_check("rescore_split_kernel (subset)");
+}
+
+// Path and workspace layout of a filtered search.  The subset path: MaxSim on
+// a bf16 (or fp32-faithful) index of 128-slot docs; everything else -- and
+// CBV2_OPT_FILTER_PATH = 2 -- scores every doc and gathers the allowed columns.
+// CBV2_OPT_FILTER_PATH = 0 takes the subset path when it is supported and
+// m <= kFilterSubsetMaxFrac * n: the largest density of the sweep at which the
+// subset path was still faster than the dense one, for both index kinds and
+// every measured B (1M docs, tools/filter_sweep.py, profiles/filter_sweep.jsonl:
+// bf16 B=1 2.41 vs 4.50 ms at 0.5 and 4.72 vs 4.50 at 1.0; B=256 76.2 vs 149.0
+// and 152.2 vs 149.9; faithful B=1 5.19 vs 10.41 and 10.60 vs 10.42 -- the
+// list's indirection costs ~5 % of a full scan).
+constexpr double kFilterSubsetMaxFrac = 0.5;
+struct FilterPlan {
+  bool subset = false;
+  size_t tk_bytes = 0, off_tk = 0, off_row = 0, off_dense = 0, off_f32 = 0, total = 0;
+};
+FilterPlan filter_plan(const cbv2_index* ix, const cbv2_filter* f, int32_t B, int32_t lq, int32_t scorer) {
+  auto r256 = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  FilterPlan p;
+  const bool supported = scorer == CBV2_SCORER_MAXSIM && ix->dtype == CBV2_DTYPE_BF16 && ix->ld == kLd;
+  p.subset = supported && (ix->filter_path == 1 ||
+                           (ix->filter_path == 0 && (double)f->m <= kFilterSubsetMaxFrac * (double)ix->n));
+  const int64_t m = f->m > 0 ? f->m : 1;
+  p.off_tk = kCtrBytes;
+  p.tk_bytes = r256(topk_ws_bytes(B, f->m));
+  p.off_row = p.off_tk + p.tk_bytes;
+  p.off_dense = p.off_row + r256((size_t)B * (size_t)m * sizeof(float));
+  p.off_f32 = p.off_dense + (p.subset ? 0 : r256((size_t)B * (size_t)(ix->n > 0 ? ix->n : 1) * sizeof(float)));
+  p.total = p.off_f32;
+  if (ix->resid != nullptr && scorer == CBV2_SCORER_MAXSIM) {
+    F32Ws w;
+    p.total += f32_ws_layout(ix, CBV2_F32_SCORE, B, lq, 0, nullptr, &w);
+  }
+  return p;
+}
 }  // namespace
 
 extern "C" {
@@ -7322,6 +7564,123 @@ int cbv2_search(cbv2_index* ix, int32_t scorer, const void* Q, int32_t q_dtype, 
   return topk_impl(sc, B, ix->n, ix->n, k, ix->id_base, rest, tk, out_scores, out_ids, st, ix->device);
 }
 
+size_t cbv2_filter_bytes(int64_t n) {
+  if (n < 0 || n > 0x7fffffffLL) return 0;
+  return filter_buf_layout(n, nullptr, nullptr, nullptr);
+}
+
+int cbv2_filter_create(const cbv2_index* ix, const uint32_t* allow, void* buf, size_t buf_bytes, void* stream,
+                       cbv2_filter** out) {
+  CBV2_REQUIRE(out != nullptr, "null output handle pointer");
+  *out = nullptr;
+  CBV2_REQUIRE(ix != nullptr, "null index");
+  CBV2_REQUIRE(ix->n <= 0x7fffffffLL, "too many docs for an int32 id list");
+  CBV2_REQUIRE(ix->n == 0 || allow != nullptr, "null allow bitmap");
+  size_t off_blk, off_off, off_total;
+  const size_t need = filter_buf_layout(ix->n, &off_blk, &off_off, &off_total);
+  CBV2_REQUIRE(buf != nullptr && buf_bytes >= need && aligned16(buf), "filter buffer too small or misaligned (%zu < %zu)",
+               buf_bytes, need);
+  DeviceGuard dg(ix->device);
+  if (!dg.ok) return fail(CBV2_EHIP, "cannot select device %d", ix->device);
+  hipStream_t st = (hipStream_t)stream;
+  int32_t m = 0;
+  if (ix->n > 0) {
+    int32_t* ids = (int32_t*)buf;
+    int32_t* blk = (int32_t*)((uint8_t*)buf + off_blk);
+    int32_t* off = (int32_t*)((uint8_t*)buf + off_off);
+    int32_t* total = (int32_t*)((uint8_t*)buf + off_total);
+    const int64_t nblk = ((ix->n + 31) / 32 + kFltWords - 1) / kFltWords;
+    hipLaunchKernelGGL(filter_count_kernel, dim3((unsigned)nblk), dim3(kFltWords), 0, st, allow, ix->n, blk);
+    int rc = launch_check("filter_count_kernel");
+    if (rc) return rc;
+    hipLaunchKernelGGL(filter_offsets_kernel, dim3(1), dim3(256), 0, st, blk, nblk, off, total);
+    if ((rc = launch_check("filter_offsets_kernel"))) return rc;
+    hipLaunchKernelGGL(filter_scatter_kernel, dim3((unsigned)nblk), dim3(kFltWords), 0, st, allow, ix->n, off, ids);
+    if ((rc = launch_check("filter_scatter_kernel"))) return rc;
+    CBV2_HIP(hipMemcpyAsync(&m, total, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    CBV2_HIP(hipStreamSynchronize(st));   // the one host round trip: m
+    if (m < 0 || m > ix->n) return fail(CBV2_EHIP, "filter compaction counted %d of %lld docs", m, (long long)ix->n);
+  }
+  auto* f = new cbv2_filter;
+  f->device = ix->device;
+  f->n = ix->n;
+  f->id_base = ix->id_base;
+  f->m = m;
+  f->ids = (const int32_t*)buf;
+  *out = f;
+  return CBV2_OK;
+}
+
+int64_t cbv2_filter_count(const cbv2_filter* f) { return f ? f->m : -1; }
+
+int cbv2_filter_destroy(cbv2_filter* f) {
+  delete f;
+  return CBV2_OK;
+}
+
+size_t cbv2_search_filtered_workspace_size(const cbv2_index* ix, const cbv2_filter* f, int32_t B, int32_t lq,
+                                           int32_t k, int32_t scorer) {
+  if (!ix || !f || B < 1 || lq < 1 || k < 1) return 0;
+  return filter_plan(ix, f, B, lq, scorer).total;
+}
+
+int cbv2_search_filtered(cbv2_index* ix, const cbv2_filter* f, int32_t scorer, const void* Q, int32_t q_dtype,
+                         int32_t B, int32_t lq, int32_t k, void* ws, size_t ws_bytes, float* out_scores,
+                         int32_t* out_ids, void* stream) {
+  CBV2_REQUIRE(f != nullptr, "null filter");
+  CBV2_REQUIRE(ix != nullptr, "null index");
+  const bool faithful = scorer == CBV2_SCORER_MAXSIM && q_dtype == CBV2_DTYPE_F32 && ix->resid != nullptr;
+  if (faithful) {
+    CBV2_REQUIRE(Q != nullptr && aligned16(Q), "query pointer must be non-null and 16-byte aligned");
+    CBV2_REQUIRE(B >= 1 && B <= 65535, "B must be in [1, 65535] (got %d)", B);
+    CBV2_REQUIRE(lq >= 1 && lq <= kLqMax, "lq must be in [1, %d] (got %d)", kLqMax, lq);
+  } else if (int rc = check_query(ix, scorer, Q, q_dtype, B, lq)) {
+    return rc;
+  }
+  CBV2_REQUIRE(f->n == ix->n && f->id_base == ix->id_base && f->device == ix->device,
+               "the filter was created for another index (n %lld / %lld, id_base %lld / %lld, device %d / %d)",
+               (long long)f->n, (long long)ix->n, (long long)f->id_base, (long long)ix->id_base, f->device, ix->device);
+  CBV2_REQUIRE(k >= 1, "k must be >= 1 (got %d)", k);
+  CBV2_REQUIRE(out_scores && out_ids, "null outputs");
+  const FilterPlan p = filter_plan(ix, f, B, lq, scorer);
+  CBV2_REQUIRE(ws != nullptr && ws_bytes >= p.total && aligned16(ws), "workspace too small or misaligned (%zu < %zu)",
+               ws_bytes, p.total);
+  DeviceGuard dg(ix->device);
+  if (!dg.ok) return fail(CBV2_EHIP, "cannot select device %d", ix->device);
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t m = f->m;
+  if (m == 0) return topk_impl_empty(B, k, out_scores, out_ids, st);   // padding only, no scan
+  int* ctr = (int*)ws;
+  float* row = (float*)((uint8_t*)ws + p.off_row);
+  float* dense = (float*)((uint8_t*)ws + p.off_dense);
+  int rc;
+  F32Ws w;
+  if (faithful) {
+    f32_ws_layout(ix, CBV2_F32_SCORE, B, lq, 0, (uint8_t*)ws + p.off_f32, &w);
+    if ((rc = split_queries(ix, (const float*)Q, B, lq, &w, st))) return rc;
+  }
+  if (p.subset) {
+    rc = faithful ? rescore_subset(ix, f, &w, B, lq, row, st)
+                  : scan_maxsim_subset(ix, f, (const uint16_t*)Q, B, lq, row, st);
+    if (rc) return rc;
+  } else {
+    rc = faithful ? launch_rescore(ix, &w, B, lq, nullptr, nullptr, ix->n, 0, dense, ix->n, st)
+                  : score_impl(ix, scorer, Q, B, lq, dense, ix->n, st, ctr);
+    if (rc) return rc;
+    const int64_t gx = std::min<int64_t>((m + 255) / 256, 4096);
+    hipLaunchKernelGGL(filter_gather_kernel, dim3((unsigned)gx, (unsigned)std::min(B, 65535)), dim3(256), 0, st, dense, ix->n,
+                       f->ids, m, B, row);
+    if ((rc = launch_check("filter_gather_kernel"))) return rc;
+  }
+  // the compact row's top-k (positions: id_base 0), then positions -> global ids
+  rc = topk_impl(row, B, m, m, k, 0, (uint8_t*)ws + p.off_tk, p.tk_bytes, out_scores, out_ids, st, ix->device);
+  if (rc) return rc;
+  const int64_t total = (int64_t)B * k;
+  hipLaunchKernelGGL(filter_map_ids_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, out_ids, total,
+                     f->ids, m, f->id_base);
+  return launch_check("filter_map_ids_kernel");
+}
+
 int cbv2_index_set_option(cbv2_index* ix, int32_t option, int64_t value) {
   CBV2_REQUIRE(ix != nullptr, "null index");
   switch (option) {
@@ -7361,6 +7720,10 @@ int cbv2_index_set_option(cbv2_index* ix, int32_t option, int64_t value) {
       return CBV2_OK;
     case CBV2_OPT_FOLD_KEYS:
       ix->fold_keys = value != 0;
+      return CBV2_OK;
+    case CBV2_OPT_FILTER_PATH:
+      if (value < 0 || value > 2) return fail(CBV2_EINVAL, "filter path must be 0 (automatic), 1 (subset) or 2 (dense)");
+      ix->filter_path = (int)value;
       return CBV2_OK;
     case CBV2_OPT_RESCORE_GRID:
       if (value < 0 || value > 65535) return fail(CBV2_EINVAL, "rescore grid must be in [0, 65535]");

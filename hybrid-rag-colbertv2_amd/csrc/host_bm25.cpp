@@ -14,6 +14,10 @@
 // float in posting order, so oracle/oracle.py:bm25_topk reproduces every bit.
 // Ranking: score descending, then doc id ascending; rows are padded with the
 // lowest-id zero-score docs (as a full sort of all docs would), then -1.
+// Filtered search (cbv2_bm25_search_filtered): a host bitmap over the local
+// docs (bit i & 31 of word i >> 5; bits past n_docs ignored); postings of docs
+// whose bit is clear are skipped, so the allowed docs accumulate the same
+// weights in the same order, and the padding takes allowed docs only.
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -133,7 +137,8 @@ extern "C" int cbv2_bm25_destroy(cbv2_bm25* ix) {
 }
 
 static void search_range(const cbv2_bm25* ix, const int32_t* q_terms, const int64_t* q_offsets, int32_t b0,
-                         int32_t b1, int32_t k, int32_t* out_ids, float* out_scores) {
+                         int32_t b1, int32_t k, const uint32_t* allow, int32_t* out_ids, float* out_scores) {
+  auto allowed = [&](int64_t d) { return allow == nullptr || ((allow[d >> 5] >> (d & 31)) & 1u) != 0u; };
   std::vector<float> acc((size_t)ix->n_docs, 0.0f);
   std::vector<int32_t> touched, terms, order;
   for (int32_t b = b0; b < b1; ++b) {
@@ -143,6 +148,7 @@ static void search_range(const cbv2_bm25* ix, const int32_t* q_terms, const int6
       if (t < 0 || t >= ix->vocab) continue;
       for (int64_t p = ix->ptr[t]; p < ix->ptr[t + 1]; ++p) {
         const int32_t d = ix->docs[p];
+        if (!allowed(d)) continue;
         if (acc[d] == 0.0f) touched.push_back(d);
         acc[d] += ix->w[p];
       }
@@ -165,6 +171,7 @@ static void search_range(const cbv2_bm25* ix, const int32_t* q_terms, const int6
       for (int64_t d = 0; d < ix->n_docs && j < k; ++d) {
         while (h < hit.size() && hit[h] < d) ++h;
         if (h < hit.size() && hit[h] == d) continue;
+        if (!allowed(d)) continue;
         oi[j] = (int32_t)d + ix->id_base;
         if (os) os[j] = 0.0f;
         ++j;
@@ -178,15 +185,16 @@ static void search_range(const cbv2_bm25* ix, const int32_t* q_terms, const int6
   }
 }
 
-extern "C" int cbv2_bm25_search(const cbv2_bm25* ix, const int32_t* q_terms, const int64_t* q_offsets, int32_t B,
-                                int32_t k, int32_t n_threads, int32_t* out_ids, float* out_scores) {
+extern "C" int cbv2_bm25_search_filtered(const cbv2_bm25* ix, const int32_t* q_terms, const int64_t* q_offsets,
+                                         int32_t B, int32_t k, int32_t n_threads, const uint32_t* allow,
+                                         int32_t* out_ids, float* out_scores) {
   if (!ix) return cbv2_set_error(CBV2_EINVAL, "null bm25 index");
   if (B < 0 || k < 1 || (B > 0 && (!q_offsets || !out_ids))) return cbv2_set_error(CBV2_EINVAL, "bad search arguments");
   if (B == 0) return CBV2_OK;
   int32_t T = n_threads > 0 ? n_threads : (int32_t)std::min<unsigned>(16u, std::max(1u, std::thread::hardware_concurrency()));
   if (T > B) T = B;
   if (T <= 1) {
-    search_range(ix, q_terms, q_offsets, 0, B, k, out_ids, out_scores);
+    search_range(ix, q_terms, q_offsets, 0, B, k, allow, out_ids, out_scores);
     return CBV2_OK;
   }
   std::vector<std::thread> pool;
@@ -194,10 +202,15 @@ extern "C" int cbv2_bm25_search(const cbv2_bm25* ix, const int32_t* q_terms, con
   for (int32_t t = 0; t < T; ++t) {
     const int32_t b0 = t * per, b1 = std::min(B, b0 + per);
     if (b0 >= b1) break;
-    pool.emplace_back(search_range, ix, q_terms, q_offsets, b0, b1, k, out_ids, out_scores);
+    pool.emplace_back(search_range, ix, q_terms, q_offsets, b0, b1, k, allow, out_ids, out_scores);
   }
   for (auto& th : pool) th.join();
   return CBV2_OK;
+}
+
+extern "C" int cbv2_bm25_search(const cbv2_bm25* ix, const int32_t* q_terms, const int64_t* q_offsets, int32_t B,
+                                int32_t k, int32_t n_threads, int32_t* out_ids, float* out_scores) {
+  return cbv2_bm25_search_filtered(ix, q_terms, q_offsets, B, k, n_threads, nullptr, out_ids, out_scores);
 }
 
 extern "C" int64_t cbv2_bm25_num_docs(const cbv2_bm25* ix) { return ix ? ix->n_docs : -1; }

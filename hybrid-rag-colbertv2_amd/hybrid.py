@@ -84,6 +84,11 @@ class ChunkStore:
     def get(self, chunk_id: int) -> Optional[Dict]:
         return self._rows.get(int(chunk_id))
 
+    def ids_of_document(self, document_id) -> List[int]:
+        """Ascending chunk ids of one uploaded document (a filter for
+        ``HybridRetriever.retrieve(allowed_ids=...)``)."""
+        return sorted(cid for cid, row in self._rows.items() if row["document_id"] == document_id)
+
     def __len__(self):
         return len(self._rows)
 
@@ -132,20 +137,25 @@ class HybridRetriever:
         if self.verbose:
             print(msg)
 
-    def retrieve(self, query: str, top_k_final: int = None) -> List[Dict]:
-        """LRC:894-935, same stages, cut-offs and per-stage timing prints."""
+    def retrieve(self, query: str, top_k_final: int = None, allowed_ids=None) -> List[Dict]:
+        """LRC:894-935, same stages, cut-offs and per-stage timing prints.
+
+        ``allowed_ids`` (a ``DocFilter`` or an iterable of chunk ids, e.g.
+        ``ChunkStore.ids_of_document``): stages 1 and 2 rank only those
+        chunks, so the fused candidates and the rerank stay inside them."""
         if top_k_final is None:
             top_k_final = self.config.final_top_k
         self._log("\n🔍 Retrieving relevant chunks...")
+        flt = None if allowed_ids is None else self.indexer.colbert_retriever._as_filter(allowed_ids)
 
         start = time.time()
-        bm25_results = self._bm25_search(query, k=self.config.bm25_top_k)
+        bm25_results = self._bm25_search(query, k=self.config.bm25_top_k, flt=flt)
         bm25_time = time.time() - start
         self._log(f"   • BM25s: {bm25_time:.3f}s")
 
         start = time.time()
         q_emb = self.indexer.colbert_retriever._encode_query(query)
-        colbert_results = self._colbert_search(q_emb, k=self.config.colbert_top_k)
+        colbert_results = self._colbert_search(q_emb, k=self.config.colbert_top_k, flt=flt)
         colbert_time = time.time() - start
         self._log(f"   • ColBERT: {colbert_time:.3f}s")
 
@@ -169,7 +179,16 @@ class HybridRetriever:
         self._log(f"   ✓ Total retrieval: {total:.3f}s")
         return reranked_results
 
-    def _bm25_search(self, query: str, k: int) -> List[Dict]:
+    @staticmethod
+    def _bm25_allow(bm, flt) -> np.ndarray:
+        """The filter as a bool mask over the BM25 index's docs (chunk id = doc id)."""
+        n = int(getattr(bm, "n_docs", flt.index.n))
+        ids = flt.ids.cpu().numpy()
+        mask = np.zeros(n, np.bool_)
+        mask[ids[ids < n]] = True
+        return mask
+
+    def _bm25_search(self, query: str, k: int, flt=None) -> List[Dict]:
         """LRC:937-950 against the host BM25."""
         bm = self.indexer.bm25_retriever
         if bm is None:
@@ -179,13 +198,19 @@ class HybridRetriever:
         # retriever with its own tokenize() (HostBM25, test stand-ins) supplies it
         tok = getattr(bm, "tokenize", None)
         query_tokens = tok(query) if callable(tok) else tokenize(query, stopwords="en", stemmer=Stemmer("english"))
-        results, scores = bm.retrieve(query_tokens, k=k)
+        if flt is None:
+            results, scores = bm.retrieve(query_tokens, k=k)
+        else:
+            results, scores = bm.retrieve(query_tokens, k=k, allow=self._bm25_allow(bm, flt))
         return [{"chunk_id": int(results[0][i]), "score": float(scores[0][i]), "source": "bm25"}
                 for i in range(len(results[0])) if results[0][i] >= 0]
 
-    def _colbert_search(self, query, k: int) -> List[Dict]:
+    def _colbert_search(self, query, k: int, flt=None) -> List[Dict]:
         """LRC:952-958."""
-        results = self.indexer.colbert_retriever.search(query=query, k=k)
+        if flt is None:
+            results = self.indexer.colbert_retriever.search(query=query, k=k)
+        else:
+            results = self.indexer.colbert_retriever.search(query=query, k=k, allowed_ids=flt)
         return [{"chunk_id": r["document_id"], "score": r["score"], "source": "colbert"} for r in results]
 
     def _reciprocal_rank_fusion(self, bm25_results: List[Dict], colbert_results: List[Dict],
@@ -243,14 +268,24 @@ class HybridRetriever:
         return final
 
     # ------------------------------------------------------------------ batched path
-    def retrieve_batch(self, Q: torch.Tensor, bm25_ids: np.ndarray, top_k_final: Optional[int] = None):
+    def retrieve_batch(self, Q: torch.Tensor, bm25_ids: np.ndarray, top_k_final: Optional[int] = None, filter=None):
         """All three stages for B query embeddings at once (the benchmark step).
 
         Q [B, lq, D] device; bm25_ids [B, kb] host int (stage-1 output) ->
         device (scores [B, k], global ids [B, k]).
+        ``filter`` (a ``DocFilter`` or chunk ids): stage 2 ranks only those
+        chunks; ``bm25_ids`` must come from a stage 1 under the same filter
+        (``HostBM25.retrieve(allow=)``).  Filtered batches take the separate
+        calls (search, host fusion, rerank), not the one-trip path.
         """
         k_final = top_k_final or self.config.final_top_k
         retr = self.indexer.colbert_retriever
+        if filter is not None:
+            _, ids = retr.search_embeddings(Q, self.config.colbert_top_k, allowed_ids=filter)
+            cand = rrf_fuse(bm25_ids, ids.cpu().numpy(), rrf_k=self.config.rrf_k, C=self.config.fused_candidates)
+            cand_d = torch.from_numpy(cand).to(retr.device)
+            s, i, _ = retr.rerank_ids(Q, cand_d, k_final)
+            return s, i
         if retr.scorer == "maxsim":       # one host round trip (cbv2_retrieve_begin / _finish), same results
             key = (id(retr.corpus_embeddings), self.config.colbert_top_k, self.config.fused_candidates, k_final,
                    self.config.rrf_k)

@@ -182,6 +182,86 @@ def quantize_mxfp8(x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     return q.view(*x.shape[:-1], DIM), sc.view(*x.shape[:-1], 2)
 
 
+def pack_allow(mask_or_ids, n: int, id_base: int = 0) -> torch.Tensor:
+    """The allow bitmap of a doc filter: ``ceil(n / 32)`` uint32 words, doc i
+    allowed when bit ``i & 31`` of word ``i >> 5`` is set (bits past n clear).
+
+    ``mask_or_ids``: a bool mask [n] over the shard's local docs, or integer
+    GLOBAL doc ids (a tensor, array or iterable; ids outside
+    ``[id_base, id_base + n)`` raise ValueError).  CPU or device tensors; the
+    words stay on the input's device."""
+    n = int(n)
+    t = mask_or_ids if isinstance(mask_or_ids, torch.Tensor) else torch.as_tensor(
+        mask_or_ids if hasattr(mask_or_ids, "__array__") else list(mask_or_ids))
+    if t.dtype == torch.bool:
+        if t.dim() != 1 or t.shape[0] != n:
+            raise ValueError(f"an allow mask must be bool [{n}] (got {tuple(t.shape)})")
+        mask = t
+    else:
+        if t.numel() and (t.is_floating_point() or t.is_complex()):
+            raise ValueError("allowed ids must be integers (or pass a bool mask)")
+        ids = t.reshape(-1).to(torch.int64)
+        if ids.numel() and (int(ids.min()) < id_base or int(ids.max()) >= id_base + n):
+            raise ValueError(f"allowed ids must lie in [{id_base}, {id_base + n})")
+        mask = torch.zeros(n, dtype=torch.bool, device=ids.device)
+        mask[ids - id_base] = True
+    nw = (n + 31) // 32
+    bits = torch.zeros(nw * 32, dtype=torch.int32, device=mask.device)
+    bits[:n] = mask.to(torch.int32)
+    # int32 arithmetic wraps, so bit 31 is the sign bit of the same word
+    weights = torch.tensor([1 << j for j in range(31)] + [-(1 << 31)], dtype=torch.int32, device=mask.device)
+    words = (bits.view(nw, 32) * weights).sum(dim=1, dtype=torch.int32)
+    return words.view(torch.uint32)
+
+
+class DocFilter:
+    """A doc filter of one ``ColbertIndex`` (cbv2_filter_create): the allow
+    bitmap compacted on the device into the ascending list of allowed ids.
+    Read-only; reusable across searches and streams of that index.  Creating
+    one waits for the device once (the count)."""
+
+    def __init__(self, index: "ColbertIndex", words: torch.Tensor):
+        L = _lib.lib()
+        self.index = index
+        nw = (index.n + 31) // 32
+        words = words.to(index.device).contiguous()
+        if words.dtype not in (torch.uint32, torch.int32) or words.numel() != nw:
+            raise ValueError(f"allow words must be uint32 [{nw}] (pack_allow)")
+        self.words = words
+        need = int(L.cbv2_filter_bytes(index.n))
+        self._buf = torch.empty((max(need, 16),), dtype=torch.uint8, device=index.device)
+        h = ctypes.c_void_p()
+        _lib.check(L.cbv2_filter_create(index._h, words.data_ptr() if nw else None, self._buf.data_ptr(),
+                                        self._buf.numel(), _stream_ptr(index.device), ctypes.byref(h)))
+        self._h = h
+        self.count = int(L.cbv2_filter_count(h))
+        self._ws: Optional[torch.Tensor] = None
+
+    @property
+    def local_ids(self) -> torch.Tensor:
+        """int32 [count] ascending LOCAL ids (a view of the filter's device buffer)."""
+        return self._buf[: 4 * self.count].view(torch.int32)
+
+    @property
+    def ids(self) -> torch.Tensor:
+        """int64 [count] ascending GLOBAL ids of the allowed docs (device)."""
+        return self.local_ids.to(torch.int64) + self.index.id_base
+
+    def close(self) -> None:
+        if getattr(self, "_h", None) is not None and self._h.value:
+            _lib.lib().cbv2_filter_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __len__(self):
+        return self.count
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class ColbertIndex:
     """One shard of the corpus resident in HBM, with a C handle borrowing it.
 
@@ -536,9 +616,56 @@ class ColbertIndex:
                                          out.shape[1], _stream_ptr(self.device)))
         return out[:, : self.n]
 
+    def filter(self, ids=None, mask=None) -> DocFilter:
+        """A ``DocFilter`` of this shard from GLOBAL doc ids or a bool mask [n]
+        over its local docs (exactly one of the two)."""
+        if (ids is None) == (mask is None):
+            raise ValueError("filter() takes ids or mask, not both")
+        return DocFilter(self, pack_allow(ids if mask is None else torch.as_tensor(mask, dtype=torch.bool),
+                                          self.n, self.id_base))
+
+    def _search_filtered(self, Q: torch.Tensor, k: int, scorer: str, flt: DocFilter):
+        """Top-k of the allowed docs (cbv2_search_filtered; asynchronous)."""
+        if not isinstance(flt, DocFilter):
+            raise TypeError("filter must be a DocFilter (ColbertIndex.filter)")
+        if not flt._h.value:
+            raise ValueError("the filter is closed")
+        k = int(k)
+        if self._query_blocks(Q, scorer) is not None:
+            # long queries: summed block scores, column gather, radix top-k, id map
+            if flt.index is not self and (flt.index.n, flt.index.id_base, flt.index.device) != \
+                    (self.n, self.id_base, self.device):
+                raise ValueError("the filter was created for another index")
+            out_s = torch.full((int(Q.shape[0]) if Q.dim() == 3 else 1, k), float("-inf"), dtype=torch.float32,
+                               device=self.device)
+            out_i = torch.full(out_s.shape, -1, dtype=torch.int32, device=self.device)
+            if flt.count == 0:
+                return out_s, out_i
+            loc = flt.local_ids.to(torch.int64)
+            row = self.score(Q, scorer).index_select(1, loc).contiguous()
+            s, p = topk_rows(row, k, id_base=0)
+            gid = (loc[p.clamp(min=0).to(torch.int64)] + self.id_base).to(torch.int32)
+            return s, torch.where(p >= 0, gid, torch.full_like(gid, -1))
+        sid = self._scorer(scorer)
+        _keep, qptr, qdt, B, lq = self._prep_query(Q, scorer)
+        L = _lib.lib()
+        need = int(L.cbv2_search_filtered_workspace_size(self._h, flt._h, B, lq, k, sid))
+        if self._ws is None or self._ws.numel() * 4 < need:
+            self._ws = torch.empty(((need + 3) // 4,), dtype=torch.float32, device=self.device)
+        out_s = torch.empty((B, k), dtype=torch.float32, device=self.device)
+        out_i = torch.empty((B, k), dtype=torch.int32, device=self.device)
+        _lib.check(L.cbv2_search_filtered(self._h, flt._h, sid, qptr, qdt, B, lq, k, self._ws.data_ptr(),
+                                          self._ws.numel() * 4, out_s.data_ptr(), out_i.data_ptr(),
+                                          _stream_ptr(self.device)))
+        return out_s, out_i
+
     def search(self, Q: torch.Tensor, k: int, scorer: str = "maxsim",
-               lb_reduce=None) -> Tuple[torch.Tensor, torch.Tensor]:
+               lb_reduce=None, filter: Optional[DocFilter] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """Top-k over the shard: (f32 [B, k] scores, int32 [B, k] global ids), -inf/-1 padded.
+
+        ``filter`` (a ``DocFilter`` of this index, ``ColbertIndex.filter``): the
+        top-k of the allowed docs only, their scores those of the unfiltered
+        scorer bit for bit; not combinable with ``lb_reduce``.
 
         ``lb_reduce`` (fp32-faithful index, sharded corpus): called with the
         exact faithful scores of this shard's bf16 top-k (device f32 [B, k]);
@@ -547,6 +674,10 @@ class ColbertIndex:
         rescores only the docs that can reach the global top-k and returns its
         part of it, which the merge completes (cbv2_search_f32_begin /
         _finish)."""
+        if filter is not None:
+            if lb_reduce is not None:
+                raise ValueError("filter cannot be combined with lb_reduce (sharded faithful filtering is out of scope)")
+            return self._search_filtered(Q, k, scorer, filter)
         if self._query_blocks(Q, scorer) is not None:   # long queries: summed block scores + radix top-k
             return topk_rows(self.score(Q, scorer), int(k), id_base=self.id_base)
         sid = self._scorer(scorer)

@@ -27,7 +27,7 @@ import torch
 
 from .config import RAGConfig
 from .encoder import encode, load_local_encoder
-from .index import ColbertIndex, IndexBuilder, select_topk
+from .index import ColbertIndex, DocFilter, IndexBuilder, select_topk
 
 
 class JinaColBERTRetriever:
@@ -164,23 +164,44 @@ class JinaColBERTRetriever:
         return q
 
     # ------------------------------------------------------------ search
-    def search(self, query: str, k: int = 10) -> List[Dict]:
-        """LRC:755-777: [{'document_id', 'score', 'text'}] best first."""
+    def make_filter(self, ids) -> DocFilter:
+        """A reusable ``DocFilter`` of the index from chunk ids (one device
+        round trip; pass it as ``allowed_ids`` to any number of searches)."""
+        if self.corpus_embeddings is None:
+            raise RuntimeError("no index: call index() or load() first")
+        return self.corpus_embeddings.filter(ids=ids)
+
+    def _as_filter(self, allowed_ids) -> Optional[DocFilter]:
+        if allowed_ids is None or isinstance(allowed_ids, DocFilter):
+            return allowed_ids
+        return self.make_filter(allowed_ids)
+
+    def search(self, query: str, k: int = 10, allowed_ids=None) -> List[Dict]:
+        """LRC:755-777: [{'document_id', 'score', 'text'}] best first.
+        ``allowed_ids`` (a ``DocFilter`` or an iterable of chunk ids): rank
+        only those chunks."""
         ix = self.corpus_embeddings
         if ix is None:
             raise RuntimeError("no index: call index() or load() first")
+        flt = self._as_filter(allowed_ids)
         q = self._encode_query(query)
-        kk = min(k, len(ix))
+        kk = min(k, len(ix)) if flt is None else min(k, flt.count)
         if kk <= 0:
             return []
-        scores, ids = ix.search(q.unsqueeze(0), kk, scorer=self.scorer)
+        if flt is None:
+            scores, ids = ix.search(q.unsqueeze(0), kk, scorer=self.scorer)
+        else:
+            scores, ids = ix.search(q.unsqueeze(0), kk, scorer=self.scorer, filter=flt)
         scores, ids = scores[0].tolist(), ids[0].tolist()  # one D2H copy each
         return [{"document_id": int(i), "score": float(s), "text": self.corpus[i] if self.corpus else None}
                 for s, i in zip(scores, ids)]
 
-    def search_embeddings(self, Q: torch.Tensor, k: int):
-        """Batched stage 2: Q [B, lq, D] -> device (scores [B, k], global ids [B, k])."""
-        return self.corpus_embeddings.search(Q, k, scorer=self.scorer)
+    def search_embeddings(self, Q: torch.Tensor, k: int, allowed_ids=None):
+        """Batched stage 2: Q [B, lq, D] -> device (scores [B, k], global ids [B, k]);
+        ``allowed_ids`` as in ``search`` (slots past the allowed count: -inf / -1)."""
+        if allowed_ids is None:
+            return self.corpus_embeddings.search(Q, k, scorer=self.scorer)
+        return self.corpus_embeddings.search(Q, k, scorer=self.scorer, filter=self._as_filter(allowed_ids))
 
     # ------------------------------------------------------------ rerank
     def rerank(self, query: str, documents: List[str], k: int = 10) -> List[Dict]:

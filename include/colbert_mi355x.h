@@ -187,6 +187,12 @@ int cbv2_index_scan_clock(cbv2_index* index, int64_t* out4, int32_t reset);
  *                        keys into its 4 x 1 scan (atomic max into keys the
  *                        query split zeroes; 0: a pass over the scores).
  *                        Identical results.
+ *  CBV2_OPT_FILTER_PATH   cbv2_search_filtered's path: 0 automatic (the subset
+ *                        path where it is supported and m <= 0.5 n, the
+ *                        largest measured density at which it still beat the
+ *                        dense path: DESIGN.md 3.8), 1 the subset path where
+ *                        supported, 2 the dense path (score every doc, gather
+ *                        the allowed columns).  Identical results.
  * cbv2_index_last_scan_plan: the work split of this handle's latest scan
  * launch: {workgroups, static chunk docs, static docs, dynamic tail 0/1}.
  * Thread safety: one handle may be used from several host threads and
@@ -205,6 +211,7 @@ int cbv2_index_scan_clock(cbv2_index* index, int64_t* out4, int32_t reset);
 #define CBV2_OPT_DENSE_DOCS 11
 #define CBV2_OPT_P1_COLLECT_FUSED 12
 #define CBV2_OPT_FOLD_KEYS 13
+#define CBV2_OPT_FILTER_PATH 14
 int cbv2_index_set_option(cbv2_index* index, int32_t option, int64_t value);
 int cbv2_index_last_scan_plan(const cbv2_index* index, int64_t* out4);
 /* Per-query workgroup lists a cbv2_search of (B, k, scorer) keeps with the
@@ -262,6 +269,57 @@ size_t cbv2_search_workspace_bytes(const cbv2_index* index, int32_t B);
 int cbv2_search(cbv2_index* index, int32_t scorer, const void* Q, int32_t q_dtype, int32_t B,
                 int32_t lq, int32_t k, void* workspace, size_t workspace_bytes,
                 float* out_scores, int32_t* out_ids, void* stream);
+
+/* Filtered search (no reference counterpart: the reference ranks its whole
+ * corpus, but its chunks carry a document_id, a heading_path and metadata --
+ * local_rag_complete.py's ChunkStore -- and a RAG application asks about one
+ * document, one tenant, a metadata predicate).  A filter is a bitmap over the
+ * shard's LOCAL docs: ceil(n / 32) uint32 words on the device, doc i allowed
+ * when bit i & 31 of word i >> 5 is set; bits at positions >= n are ignored.
+ * One filter serves a whole call (no per-query filters).
+ *  - cbv2_filter_create compacts the bitmap into the ascending list of the
+ *    allowed local ids (popcount per word, prefix sum over the words, scatter)
+ *    in `buf`, a caller-owned DEVICE buffer of cbv2_filter_bytes(n) bytes
+ *    (16-B aligned) the handle borrows until cbv2_filter_destroy; `allow` is
+ *    read during the call only.  It then WAITS on `stream` once to read m, the
+ *    number of allowed docs (cbv2_filter_count): the only host round trip, so
+ *    create is NOT capturable.  The handle is read-only afterwards (several
+ *    streams may share it) and remembers the index's n, id_base and device:
+ *    passing it with an index that differs in any of those is CBV2_EINVAL.
+ *  - cbv2_search_filtered: cbv2_search (bf16 / MXFP8 queries, either scorer)
+ *    or the faithful search (an fp32-faithful index with q_dtype
+ *    CBV2_DTYPE_F32, Q f32 [B][lq][128]) over the allowed docs only: their
+ *    top-k, score descending then id ascending; out_scores f32 [B][k],
+ *    out_ids int32 [B][k] (global ids); slots past min(k, m) hold -inf / -1;
+ *    m == 0 writes only that padding and launches no scan.  The scores are
+ *    the unfiltered scorer's for those docs, bit for bit (cbv2_score;
+ *    cbv2_score_f32 for the faithful search); an allowed doc with doclens == 0
+ *    scores -inf, keeps its id and ranks after every finite score.
+ *    Asynchronous and capturable.  Workspace (16-B aligned, one per stream):
+ *    cbv2_search_filtered_workspace_size(index, filter, B, lq, k, scorer)
+ *    bytes, computed with the options the search will run under.
+ *    Two paths, same results (CBV2_OPT_FILTER_PATH):
+ *    subset -- MaxSim on a bf16 or fp32-faithful index of 128-slot docs: the
+ *      scan walks the id list (doc lengths and base addresses through it) and
+ *      writes a compact row [B][m] -- B <= 2 the streaming scan, moving only
+ *      the listed docs' token tiles; larger B the doc-interleaved MFMA scans,
+ *      each listed doc loaded once per query group; faithful: one faithful
+ *      score (lo.qhi + hi.qlo + hi.qhi in one kernel) per (query, allowed doc);
+ *    dense -- everything else (MXFP8, long documents, REF_MEANPOOL_COSINE):
+ *      the full scorer into [B][n], then a gather of the allowed columns.
+ *    Both end in the row top-k and a map of row positions to
+ *    id_base + ids[pos] (the list is ascending: position order is id order). */
+typedef struct cbv2_filter cbv2_filter;
+size_t cbv2_filter_bytes(int64_t n);
+int cbv2_filter_create(const cbv2_index* index, const uint32_t* allow, void* buf, size_t buf_bytes, void* stream,
+                       cbv2_filter** out);
+int64_t cbv2_filter_count(const cbv2_filter* filter);
+int cbv2_filter_destroy(cbv2_filter* filter);
+size_t cbv2_search_filtered_workspace_size(const cbv2_index* index, const cbv2_filter* filter, int32_t B, int32_t lq,
+                                           int32_t k, int32_t scorer);
+int cbv2_search_filtered(cbv2_index* index, const cbv2_filter* filter, int32_t scorer, const void* Q, int32_t q_dtype,
+                         int32_t B, int32_t lq, int32_t k, void* workspace, size_t workspace_bytes,
+                         float* out_scores, int32_t* out_ids, void* stream);
 
 /* cbv2_rerank — JinaColBERTRetriever.rerank (local_rag_complete.py:779-800)
  * without re-encoding: the C candidate docs of each query are GATHERED from
@@ -412,6 +470,15 @@ int cbv2_bm25_build(const int32_t* doc_terms, const int64_t* doc_offsets, int64_
                     float k1, float b, cbv2_bm25** out);
 int cbv2_bm25_search(const cbv2_bm25* index, const int32_t* q_terms, const int64_t* q_offsets, int32_t B,
                      int32_t k, int32_t n_threads, int32_t* out_ids, float* out_scores);
+/* cbv2_bm25_search_filtered: the same search over the docs whose bit is set in
+ * `allow` (HOST, ceil(n_docs / 32) words over the LOCAL docs, the bit order of
+ * cbv2_filter_create; bits past n_docs ignored): same weights, accumulation
+ * order and tie rule; a doc whose bit is clear never enters the selection, and
+ * the zero-score padding takes the lowest-id ALLOWED docs that scored 0, then
+ * -1.  allow == NULL is cbv2_bm25_search.                                  */
+int cbv2_bm25_search_filtered(const cbv2_bm25* index, const int32_t* q_terms, const int64_t* q_offsets, int32_t B,
+                              int32_t k, int32_t n_threads, const uint32_t* allow, int32_t* out_ids,
+                              float* out_scores);
 /* Sharded BM25 (no reference counterpart): a rank indexes
  * only its doc range [id_base, id_base + n_docs) but with the GLOBAL
  * statistics (n_global docs, total_global tokens, df_global [vocab] from an
