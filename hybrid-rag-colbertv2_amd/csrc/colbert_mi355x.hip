@@ -6092,6 +6092,19 @@ hipError_t zero_ctr_block(int* ctr, hipStream_t st) {
   return hipGetLastError();
 }
 
+// Whether `st` is recording a hipGraph.  What a captured call leaves in the
+// handle would be frozen into every replay, so the handle's own per-launch
+// state (the counter ring and its events, the timing events) is kept out of
+// a capture.  A stream the runtime cannot query counts as not capturing.
+bool stream_capturing(hipStream_t st) {
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(st, &cs) != hipSuccess) {
+    (void)hipGetLastError();
+    return false;
+  }
+  return cs == hipStreamCaptureStatusActive;
+}
+
 int plan_split(cbv2_index* ix, int nq_groups, int64_t target, float dyn_frac, int task_docs, hipStream_t st,
                ScanSplit* sp, int* ctr_ws) {
   int64_t n_chunks = target / nq_groups;   // never more workgroups than resident slots
@@ -6101,10 +6114,14 @@ int plan_split(cbv2_index* ix, int nq_groups, int64_t target, float dyn_frac, in
   sp->ctr = nullptr;
   sp->ring_slot = -1;
   const int64_t tail_chunk = ((int64_t)((double)ix->n * (1.0 - (double)dyn_frac)) / n_chunks) & ~(int64_t)63;
-  const bool have_ctr = ctr_ws != nullptr || ix->task_ring != nullptr;
   sp->slices = ix->dynamic_tail == 2 ? 1 : kTailSlices;
-  if (have_ctr && ix->dynamic_tail && dyn_frac > 0.0f && nq_groups * sp->slices <= kRingInts &&
-      tail_chunk >= kMinChunkDocs) {
+  const bool want_tail = ix->dynamic_tail && dyn_frac > 0.0f && nq_groups * sp->slices <= kRingInts &&
+                         tail_chunk >= kMinChunkDocs;
+  // A capturing cbv2_score takes no ring slot: the slot and its event would be
+  // frozen into the graph, and the eager launch that draws the same slot 128
+  // calls later could not be ordered against the graph's replays.  It runs
+  // the static split instead (the scores do not depend on the split).
+  if (want_tail && (ctr_ws != nullptr || (ix->task_ring != nullptr && !stream_capturing(st)))) {
     sp->chunk_docs = tail_chunk;
     sp->static_docs = sp->chunk_docs * n_chunks;
     if (ctr_ws != nullptr) {
@@ -6762,10 +6779,12 @@ int check_query(cbv2_index* ix, int32_t scorer, const void* Q, int32_t q_dtype, 
 
 // Start/stop events of the next timed scan, reserved under the handle's mutex
 // (false when timing is off or an event cannot be created: the scan then runs
-// untimed).
-bool scan_event_pair(cbv2_index* ix, hipEvent_t* e0, hipEvent_t* e1) {
+// untimed).  A launch on a capturing stream is not timed either: an event
+// recorded inside a capture has no time to read back, and the graph's replays
+// are launches this record never saw.
+bool scan_event_pair(cbv2_index* ix, hipStream_t st, hipEvent_t* e0, hipEvent_t* e1) {
   std::lock_guard<std::mutex> lk(ix->mu);
-  if (!ix->time_scans) return false;
+  if (!ix->time_scans || stream_capturing(st)) return false;
   const size_t i = ix->scan_ev_used;
   while (ix->scan_ev.size() < 2 * i + 2) {
     hipEvent_t e;
@@ -6781,7 +6800,7 @@ bool scan_event_pair(cbv2_index* ix, hipEvent_t* e0, hipEvent_t* e1) {
 int scan_maxsim_timed(cbv2_index* ix, const void* Q, int32_t B, int32_t lq, float* out, int64_t ld_out,
                       hipStream_t st, int* ctr_ws = nullptr, FusedTopk* ft = nullptr, uint32_t* bm = nullptr) {
   hipEvent_t e0 = nullptr, e1 = nullptr;
-  const bool timed = scan_event_pair(ix, &e0, &e1);
+  const bool timed = scan_event_pair(ix, st, &e0, &e1);
   if (timed && hipEventRecord(e0, st) != hipSuccess) return fail(CBV2_EHIP, "hipEventRecord failed");
   g_clock_probe = timed && ix->clock_on ? ix->clk : nullptr;
   const int rc = ix->dtype == CBV2_DTYPE_MXFP8
@@ -6795,10 +6814,11 @@ int scan_maxsim_timed(cbv2_index* ix, const void* Q, int32_t B, int32_t lq, floa
 
 // Band timing marks (cbv2_index_band_times): start after the bf16 top-k of a
 // faithful search, stop after its band select / fallback.  A stop without a
-// recorded start (timing switched on in between) records nothing.
+// recorded start (timing switched on in between) records nothing, and neither
+// does a mark on a capturing stream (as for the scans).
 int band_mark(cbv2_index* ix, bool stop, hipStream_t st) {
   std::lock_guard<std::mutex> lk(ix->mu);
-  if (!ix->time_scans) return CBV2_OK;
+  if (!ix->time_scans || stream_capturing(st)) return CBV2_OK;
   const size_t i = ix->band_ev_used;
   if (!stop) {
     while (ix->band_ev.size() < 2 * i + 2) {

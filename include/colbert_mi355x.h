@@ -15,10 +15,33 @@
  *    declaration says HOST: the host-only helpers (cbv2_rrf_fuse, BM25, the
  *    index file, the stemmer) and the stage-1 lists / host stage of
  *    cbv2_retrieve_finish.  Nothing is allocated or freed inside a compute
- *    call; every call but cbv2_retrieve_finish (which waits for its round
- *    trip) is asynchronous and hipGraph-capturable.
+ *    call.
  *  - Calls are asynchronous on `stream` (a hipStream_t; NULL = legacy default
  *    stream).  One index handle belongs to one device.
+ *  - hipGraph capture.  These calls may be issued on a capturing stream, and
+ *    every replay of the graph recomputes them from the buffers' contents at
+ *    replay time (tests/test_gpu_graph_replay.py replays each of them over
+ *    poisoned workspaces and outputs):
+ *      cbv2_score, cbv2_score_f32, cbv2_quantize_mxfp8,
+ *      cbv2_search, cbv2_search_f32, cbv2_search_filtered (the filter created
+ *      before the capture),
+ *      cbv2_rerank, cbv2_rerank_ws, cbv2_rerank_f32,
+ *      cbv2_select_topk, cbv2_topk_rows, cbv2_merge_topk, cbv2_split_f32.
+ *    A replay re-initialises every counter and flag it uses in the caller's
+ *    workspace; a graph and the eager calls between its replays may share a
+ *    handle and, on one stream, a workspace.  What the handle itself owns per
+ *    launch stays out of a capture:
+ *      - a capturing cbv2_score takes no slot of the handle's task-counter
+ *        ring and runs the static work split, without the dynamic tail (the
+ *        scores are the same bit for bit; searches keep their tail: their
+ *        counters are in the caller's workspace);
+ *      - with cbv2_index_time_scans enabled, launches on a capturing stream
+ *        are not timed: cbv2_index_scan_times / _band_times report the eager
+ *        launches only, never a graph's replays.
+ *    Outside the list, not to be captured: cbv2_retrieve_* (pooled mapped buffers, a second stream
+ *    and host polling), the sharded and loopback calls, cbv2_filter_create
+ *    (waits for its count), the index-file, writer and cbv2_hbm_* calls, and
+ *    cbv2_index_build_means.
  *  - Return 0 on success, a negative CBV2_E* code on error; the message is in
  *    the thread-local `cbv2_last_error()`.  Arguments are validated on the host
  *    BEFORE any launch: a call that returns an error has launched nothing.
@@ -101,7 +124,8 @@ int cbv2_hbm_free(int device, void* p);
  * enabled, every MaxSim scan launch of this handle (cbv2_score / cbv2_search /
  * cbv2_search_f32) is bracketed by HIP events recorded on the launch's own
  * stream, so a benchmark can time the dominant kernel inside its timed region
- * without a side launch.  enable=1 clears the previous record.
+ * without a side launch.  enable=1 clears the previous record.  Launches on
+ * a stream that is capturing a hipGraph are not timed (Conventions).
  * cbv2_index_scan_times (timing disabled first) waits for the recorded launches
  * and writes min(count, max) durations in ms; *count = launches recorded;
  * the record is then cleared.
