@@ -227,6 +227,26 @@ class NativeBM25:
                                                ids.ctypes.data, sc.ctypes.data))
         return ids, sc
 
+    def search_batch(self, q_terms: np.ndarray, q_offsets: np.ndarray, k: int, allows, n_threads: int = 0):
+        """Per-query filters (cbv2_bm25_search_filtered_batch): ``allows`` holds
+        one entry per query -- a bool mask, packed uint32 words, or ``None`` for
+        an unfiltered query.  Row b equals ``search`` of query b under allows[b]."""
+        q_terms = np.ascontiguousarray(q_terms, np.int32)
+        q_offsets = np.ascontiguousarray(q_offsets, np.int64)
+        B = len(q_offsets) - 1
+        if len(allows) != B:
+            raise ValueError(f"allows must hold one entry per query ({len(allows)} for {B} queries)")
+        ids = np.empty((B, k), np.int32)
+        sc = np.empty((B, k), np.float32)
+        nw = (self.n_docs + 31) // 32
+        words = [self._allow_words(a) for a in allows]                 # kept alive over the call
+        words = [np.zeros(1, np.uint32) if (w is not None and nw == 0) else w for w in words]
+        ptrs = (ctypes.c_void_p * max(B, 1))(*[None if w is None else w.ctypes.data for w in words])
+        _lib.check(_lib.lib().cbv2_bm25_search_filtered_batch(
+            self._h, q_terms.ctypes.data if q_terms.size else None, q_offsets.ctypes.data, B, int(k),
+            int(n_threads), ptrs, ids.ctypes.data, sc.ctypes.data))
+        return ids, sc
+
 
 def sharded(doc_terms: np.ndarray, doc_offsets: np.ndarray, vocab: int, id_base: int, group=None,
             device=None, k1: float = 1.5, b: float = 0.75) -> NativeBM25:
@@ -311,6 +331,16 @@ class HostBM25:
             raise RuntimeError("BM25 index not built: call index() or load() first")
         q, off = to_csr([self._ids(t, grow=False) for t in self._rows(query_tokens)])
         ids, sc = self._native.search(q, off, k, n_threads, allow=allow)
+        return ids.astype(np.int64), sc
+
+    def retrieve_batch(self, query_tokens, allows, k: int = 10, n_threads: int = 0):
+        """``retrieve`` with one filter per query: ``allows[b]`` (a bool mask,
+        packed words, or ``None`` = unfiltered) restricts query b
+        (``NativeBM25.search_batch``)."""
+        if self._native is None:
+            raise RuntimeError("BM25 index not built: call index() or load() first")
+        q, off = to_csr([self._ids(t, grow=False) for t in self._rows(query_tokens)])
+        ids, sc = self._native.search_batch(q, off, k, allows, n_threads)
         return ids.astype(np.int64), sc
 
     # ---------------------------------------------------------------- persistence

@@ -1480,21 +1480,53 @@ __device__ __forceinline__ int sload_len(const int32_t* p) {
 // base address go through the list (two dependent scalar loads per doc, off
 // the vmcnt count like the lengths), and its score lands in column i of the
 // compact row.  Only the listed docs' token tiles are streamed.
+// RAG (the per-query filters' ragged scan; IDX, QW = 1): every row b has its
+// own list.  A wave's work item is (row b, chunk of row b's list); `rag` is
+// the filter batch's table (fb_* offsets below) -- the exclusive prefix of the
+// rows' chunk counts, the rows' counts and the lists' addresses.  The wave
+// finds its row by a binary search of the prefix, all of it on the scalar unit
+// (s_load, lgkmcnt) and before the first LDS-DMA issue, so nothing of it ever
+// enters the ring's vmcnt count; from there n, ids and the query row are that
+// row's and the loop below is the IDX loop unchanged.  Waves past the last
+// chunk exit.
+__host__ __device__ constexpr int64_t fb_off_count(int64_t B) { return B + 1; }       // int32 [B]: m_b
+__host__ __device__ constexpr int64_t fb_off_list(int64_t B) { return 2 * B + 1; }    // int32 [B][2]: list address, lo / hi
+__host__ __device__ constexpr int64_t fb_table_ints(int64_t B) { return 4 * B + 1; }  // (prefix: int32 [B + 1] at 0)
 template <int QW, int AUX, int WAVES = 4, int SLOTS = kStreamSlots, bool TW2 = false, bool PF = false,
-          bool IDX = false>
+          bool IDX = false, bool RAG = false>
 __global__ __launch_bounds__(WAVES * 64, 1) void maxsim_scan_stream_kernel(
-    const uint8_t* __restrict__ tokens, const int32_t* __restrict__ doclens, int64_t n,
+    const uint8_t* __restrict__ tokens, const int32_t* __restrict__ doclens, int64_t n_arg,
     const uint16_t* __restrict__ Q, int B, int lq, float* __restrict__ out, int64_t ld_out, int64_t chunk_docs,
     int ld, uint32_t* __restrict__ bm, int64_t bm_ld, uint32_t* __restrict__ sb, int64_t sb_ld,
-    const int32_t* __restrict__ ids = nullptr) {
+    const int32_t* __restrict__ ids_arg = nullptr, const int32_t* __restrict__ rag = nullptr) {
+  static_assert(!RAG || (IDX && QW == 1), "the ragged scan walks one list per query");
   __shared__ __attribute__((aligned(1024))) uint8_t smem[WAVES * SLOTS * 4096];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int c = lane & 15, g = lane >> 4;
   const int nq_groups = (B + QW - 1) / QW;
   const int64_t lin = (int64_t)blockIdx.x * WAVES + wave;      // one doc chunk per wave
-  const int qg = (int)(lin % nq_groups);
-  const int64_t chunk = lin / nq_groups;
+  int qg;
+  int64_t chunk, n = n_arg;
+  const int32_t* ids = ids_arg;
+  if constexpr (RAG) {
+    const int item = (int)lin;                       // (the launcher keeps the chunk total below 2^31)
+    if (item >= sload_len(rag + B)) return;          // surplus wave of the last workgroup
+    int lo = 0, hi = B;                              // the last row whose prefix is <= item: rows without
+    while (hi - lo > 1) {                            // chunks share their successor's prefix and are passed
+      const int mid = (lo + hi) >> 1;
+      if (sload_len(rag + mid) <= item) lo = mid; else hi = mid;
+    }
+    qg = lo;
+    chunk = item - sload_len(rag + lo);
+    n = sload_len(rag + fb_off_count(B) + lo);
+    const uint32_t alo = (uint32_t)sload_len(rag + fb_off_list(B) + 2 * lo);
+    const uint32_t ahi = (uint32_t)sload_len(rag + fb_off_list(B) + 2 * lo + 1);
+    ids = reinterpret_cast<const int32_t*>(((uint64_t)ahi << 32) | alo);
+  } else {
+    qg = (int)(lin % nq_groups);
+    chunk = lin / nq_groups;
+  }
   const int64_t d_begin = chunk * chunk_docs;
   const int64_t d_end = (d_begin + chunk_docs < n) ? d_begin + chunk_docs : n;
   if (d_begin >= d_end) return;  // uniform over the wave; no block-level sync below
@@ -5772,6 +5804,7 @@ struct cbv2_index {
   bool band_open = false;
   std::vector<hipEvent_t> band_ev;
   int filter_path = 0;   // CBV2_OPT_FILTER_PATH (0: automatic, 1: subset where supported, 2: dense)
+  int64_t filter_batch_chunk_docs = 0;   // CBV2_OPT_FILTER_BATCH_CHUNK_DOCS (0: automatic), read by cbv2_filter_batch_create
 };
 
 // A doc filter (cbv2_filter_create): the ascending list of the allowed local
@@ -5782,6 +5815,20 @@ struct cbv2_filter {
   int64_t n = 0, id_base = 0;
   int64_t m = 0;                 // allowed docs
   const int32_t* ids = nullptr;  // [m] ascending local ids (head of the caller's buffer)
+};
+
+// One filter per query of a call (cbv2_filter_batch_create).  The device table
+// (the caller's buffer; layout: fb_off_* above the streaming scan) holds the
+// exclusive prefix of the rows' chunk counts under chunk_docs, the rows'
+// counts m_b and the lists' addresses.  Read-only after creation.
+struct cbv2_filter_batch {
+  int device = 0;
+  int64_t n = 0, id_base = 0;
+  int32_t B = 0;
+  int64_t pairs = 0, max_m = 0;   // sum and largest of the m_b
+  int64_t chunk_docs = 1;         // docs per (row, chunk) work item of the ragged scan
+  int64_t chunks = 0;             // work items: sum of ceil(m_b / chunk_docs)
+  const int32_t* table = nullptr;
 };
 
 namespace {
@@ -7281,26 +7328,122 @@ int rescore_subset(cbv2_index* ix, const cbv2_filter* f, const F32Ws* w, int B, 
 constexpr double kFilterSubsetMaxFrac = 0.5;
 struct FilterPlan {
   bool subset = false;
-  size_t tk_bytes = 0, off_tk = 0, off_row = 0, off_dense = 0, off_f32 = 0, total = 0;
+  size_t tk_bytes = 0, off_tk = 0, off_row = 0, off_cand = 0, off_dense = 0, off_f32 = 0, total = 0;
 };
-FilterPlan filter_plan(const cbv2_index* ix, const cbv2_filter* f, int32_t B, int32_t lq, int32_t scorer) {
+// m: the compact rows' stride (a filter's count; a filter batch's largest
+// count, which also decides the path); cand: the faithful subset path keeps a
+// per-row candidate matrix [B][m] behind the rows (per-query filters only).
+FilterPlan filter_plan_m(const cbv2_index* ix, int64_t m_allowed, bool cand, int32_t B, int32_t lq, int32_t scorer) {
   auto r256 = [](size_t b) { return (b + 255) & ~(size_t)255; };
   FilterPlan p;
   const bool supported = scorer == CBV2_SCORER_MAXSIM && ix->dtype == CBV2_DTYPE_BF16 && ix->ld == kLd;
   p.subset = supported && (ix->filter_path == 1 ||
-                           (ix->filter_path == 0 && (double)f->m <= kFilterSubsetMaxFrac * (double)ix->n));
-  const int64_t m = f->m > 0 ? f->m : 1;
+                           (ix->filter_path == 0 && (double)m_allowed <= kFilterSubsetMaxFrac * (double)ix->n));
+  const bool f32 = ix->resid != nullptr && scorer == CBV2_SCORER_MAXSIM;
+  const int64_t m = m_allowed > 0 ? m_allowed : 1;
   p.off_tk = kCtrBytes;
-  p.tk_bytes = r256(topk_ws_bytes(B, f->m));
+  p.tk_bytes = r256(topk_ws_bytes(B, m_allowed));
   p.off_row = p.off_tk + p.tk_bytes;
-  p.off_dense = p.off_row + r256((size_t)B * (size_t)m * sizeof(float));
+  p.off_cand = p.off_row + r256((size_t)B * (size_t)m * sizeof(float));
+  p.off_dense = p.off_cand + (cand && p.subset && f32 ? r256((size_t)B * (size_t)m * sizeof(int32_t)) : 0);
   p.off_f32 = p.off_dense + (p.subset ? 0 : r256((size_t)B * (size_t)(ix->n > 0 ? ix->n : 1) * sizeof(float)));
   p.total = p.off_f32;
-  if (ix->resid != nullptr && scorer == CBV2_SCORER_MAXSIM) {
+  if (f32) {
     F32Ws w;
     p.total += f32_ws_layout(ix, CBV2_F32_SCORE, B, lq, 0, nullptr, &w);
   }
   return p;
+}
+FilterPlan filter_plan(const cbv2_index* ix, const cbv2_filter* f, int32_t B, int32_t lq, int32_t scorer) {
+  return filter_plan_m(ix, f->m, false, B, lq, scorer);
+}
+
+// ---------------------------------------------------------------------------
+// Per-query filters (cbv2_filter_batch_*, cbv2_search_filtered_batch): row b
+// of a call is searched under its own filter.  The compact rows share one
+// stride M = the largest m_b; row b's columns [m_b, M) hold -inf, so the row
+// top-k over M columns ranks them after every real doc (a real -inf doc sits
+// at a lower position) and the id map turns positions >= m_b into -1.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ const int32_t* fb_list(const int32_t* __restrict__ tab, int B, int b) {
+  const uint32_t lo = (uint32_t)tab[fb_off_list(B) + 2 * b], hi = (uint32_t)tab[fb_off_list(B) + 2 * b + 1];
+  return reinterpret_cast<const int32_t*>(((uint64_t)hi << 32) | lo);
+}
+
+// The subset paths' row tails (-inf past m_b) and, for the faithful index,
+// the per-row candidate matrix of rescore_split_kernel (cand != nullptr:
+// cand[b][p] = row b's p-th allowed local id, -1 past m_b -- never read:
+// count[b] = m_b bounds the row).
+__global__ __launch_bounds__(256) void fb_prepare_kernel(const int32_t* __restrict__ tab, int B, int64_t M,
+                                                         int32_t* __restrict__ cand, float* __restrict__ row) {
+  for (int b = blockIdx.y; b < B; b += gridDim.y) {
+    const int64_t m = tab[fb_off_count(B) + b];
+    const int32_t* ids = fb_list(tab, B, b);
+    for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < M; p += (int64_t)gridDim.x * blockDim.x) {
+      if (cand != nullptr) cand[(size_t)b * M + p] = p < m ? ids[p] : -1;
+      if (p >= m) row[(size_t)b * M + p] = neg_inf();
+    }
+  }
+}
+
+// The dense path's ragged column gather: row[b][p] = dense[b][ids_b[p]], -inf past m_b.
+__global__ __launch_bounds__(256) void fb_gather_kernel(const float* __restrict__ dense, int64_t ld,
+                                                        const int32_t* __restrict__ tab, int B, int64_t M,
+                                                        float* __restrict__ row) {
+  for (int b = blockIdx.y; b < B; b += gridDim.y) {
+    const int64_t m = tab[fb_off_count(B) + b];
+    const int32_t* ids = fb_list(tab, B, b);
+    for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < M; p += (int64_t)gridDim.x * blockDim.x)
+      row[(size_t)b * M + p] = p < m ? dense[(size_t)b * ld + ids[p]] : neg_inf();
+  }
+}
+
+// Row positions of row b's top-k -> global ids through row b's list; positions
+// at or past m_b (the stride's -inf tail) and the top-k's own padding are -1.
+__global__ __launch_bounds__(256) void fb_map_ids_kernel(int32_t* __restrict__ out_i, int B, int k,
+                                                         const int32_t* __restrict__ tab, int64_t id_base) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (int64_t)B * k) return;
+  const int b = (int)(i / k);
+  const int32_t p = out_i[i];
+  out_i[i] = (p >= 0 && p < tab[fb_off_count(B) + b]) ? (int32_t)(id_base + fb_list(tab, B, b)[p]) : -1;
+}
+
+// The ragged streaming scan: one launch for every row, ceil(chunks / 4)
+// workgroups whatever B and however many distinct filters.
+int launch_stream_ragged(cbv2_index* ix, const cbv2_filter_batch* fb, const uint16_t* Q, int B, int lq, float* out,
+                         int64_t M, hipStream_t st) {
+  const int64_t grid = (fb->chunks + 3) / 4;
+  if (grid < 1 || grid > 0x1fffffff) return fail(CBV2_EUNSUPPORTED, "scan grid too large");
+  hipLaunchKernelGGL((maxsim_scan_stream_kernel<1, 2, 4, kStreamSlots, false, false, true, true>), dim3((unsigned)grid),
+                     dim3(256), 0, st, ix->tokens, ix->doclens, (int64_t)0, Q, B, lq, out, M, fb->chunk_docs,
+                     (int)ix->ld, (uint32_t*)nullptr, (int64_t)0, (uint32_t*)nullptr, (int64_t)0,
+                     (const int32_t*)nullptr, fb->table);
+  return launch_check("maxsim_scan_stream_kernel (ragged)");
+}
+
+// The faithful rows: rescore_subset's launch over the per-row candidate matrix
+// (ld_c = M, count[b] = m_b out of the table, local ids: id_base 0).
+int rescore_ragged(cbv2_index* ix, const cbv2_filter_batch* fb, const F32Ws* w, int B, int lq, const int32_t* cand,
+                   float* out, int64_t M, hipStream_t st) {
+  const int64_t grid_auto = std::min<int64_t>(kRsSplitGrid, std::max<int64_t>(256, 4096 / std::max(B, 1)));
+  const int64_t grid_max = ix->rescore_grid > 0 ? ix->rescore_grid : grid_auto;
+  const unsigned gx = (unsigned)(M < grid_max ? M : grid_max);   // a row's pairs beyond the grid stride it
+  const bool two = (int64_t)gx * B > 3LL * cu_count(ix->device);
+  auto kern = two ? rescore_split_kernel<false, 2> : rescore_split_kernel<false, 4>;
+  hipLaunchKernelGGL(kern, dim3(gx, (unsigned)B), dim3(two ? 128 : 256), 0, st, ix->tokens, ix->resid, ix->doclens,
+                     ix->n, (int64_t)0, w->qhi, w->qlo, lq, cand, fb->table + fb_off_count(B), M, M, out, M,
+                     (const int32_t*)nullptr, (int)ix->ld, (uint32_t*)nullptr, (int64_t)0, (float*)nullptr,
+                     (int32_t*)nullptr, 0, (float*)nullptr, (int32_t*)nullptr, RowSelect(), TaggedCand());
+  return launch_check("rescore_split_kernel (ragged)");
+}
+
+// Path and workspace layout of a per-query filtered search: filter_plan's
+// rule and layout with m = M, the largest m_b, plus the faithful subset
+// path's candidate matrix.
+FilterPlan filter_batch_plan(const cbv2_index* ix, const cbv2_filter_batch* fb, int32_t B, int32_t lq,
+                             int32_t scorer) {
+  return filter_plan_m(ix, fb->max_m, true, B, lq, scorer);
 }
 }  // namespace
 
@@ -7701,6 +7844,149 @@ int cbv2_search_filtered(cbv2_index* ix, const cbv2_filter* f, int32_t scorer, c
   return launch_check("filter_map_ids_kernel");
 }
 
+size_t cbv2_filter_batch_bytes(int32_t B) {
+  if (B < 1 || B > 65535) return 0;
+  return (((size_t)fb_table_ints(B) * sizeof(int32_t) + 255) & ~(size_t)255) + 256;
+}
+
+int cbv2_filter_batch_create(const cbv2_index* ix, const cbv2_filter* const* per_query, int32_t B, void* buf,
+                             size_t buf_bytes, void* stream, cbv2_filter_batch** out) {
+  CBV2_REQUIRE(out != nullptr, "null output handle pointer");
+  *out = nullptr;
+  CBV2_REQUIRE(ix != nullptr, "null index");
+  CBV2_REQUIRE(B >= 1 && B <= 65535, "B must be in [1, 65535] (got %d)", B);
+  CBV2_REQUIRE(per_query != nullptr, "null per-query filter array");
+  const size_t need = cbv2_filter_batch_bytes(B);
+  CBV2_REQUIRE(buf != nullptr && buf_bytes >= need && aligned16(buf),
+               "filter batch buffer too small or misaligned (%zu < %zu)", buf_bytes, need);
+  int64_t pairs = 0, max_m = 0;
+  for (int32_t b = 0; b < B; ++b) {
+    const cbv2_filter* f = per_query[b];
+    CBV2_REQUIRE(f != nullptr, "null filter for query %d", b);
+    CBV2_REQUIRE(f->n == ix->n && f->id_base == ix->id_base && f->device == ix->device,
+                 "the filter of query %d was created for another index (n %lld / %lld, id_base %lld / %lld, device %d / %d)",
+                 b, (long long)f->n, (long long)ix->n, (long long)f->id_base, (long long)ix->id_base, f->device,
+                 ix->device);
+    pairs += f->m;
+    max_m = std::max(max_m, f->m);
+  }
+  DeviceGuard dg(ix->device);
+  if (!dg.ok) return fail(CBV2_EHIP, "cannot select device %d", ix->device);
+  // docs per work item: as launch_stream_ids sizes its chunks -- the chip's
+  // resident waves times the oversubscription, here over all rows' pairs
+  int64_t chunk_docs = ix->filter_batch_chunk_docs;
+  if (chunk_docs <= 0) {
+    const int64_t target_waves = 4LL * cu_count(ix->device) * kDirectOversub;
+    chunk_docs = std::max<int64_t>(1, (pairs + target_waves - 1) / target_waves);
+  }
+  std::vector<int32_t> tab((size_t)fb_table_ints(B));
+  int64_t chunks = 0;
+  for (int32_t b = 0; b < B; ++b) {
+    const cbv2_filter* f = per_query[b];
+    tab[b] = (int32_t)chunks;
+    chunks += (f->m + chunk_docs - 1) / chunk_docs;
+    CBV2_REQUIRE(chunks <= 0x7ffffff0LL, "too many work items: raise CBV2_OPT_FILTER_BATCH_CHUNK_DOCS");
+    tab[fb_off_count(B) + b] = (int32_t)f->m;
+    const uint64_t a = (uint64_t)(uintptr_t)f->ids;
+    tab[fb_off_list(B) + 2 * b] = (int32_t)(uint32_t)a;
+    tab[fb_off_list(B) + 2 * b + 1] = (int32_t)(uint32_t)(a >> 32);
+  }
+  tab[B] = (int32_t)chunks;
+  hipStream_t st = (hipStream_t)stream;
+  CBV2_HIP(hipMemcpyAsync(buf, tab.data(), tab.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  CBV2_HIP(hipStreamSynchronize(st));   // the table is on the device (and the host copy may go)
+  auto* fb = new cbv2_filter_batch;
+  fb->device = ix->device;
+  fb->n = ix->n;
+  fb->id_base = ix->id_base;
+  fb->B = B;
+  fb->pairs = pairs;
+  fb->max_m = max_m;
+  fb->chunk_docs = chunk_docs;
+  fb->chunks = chunks;
+  fb->table = (const int32_t*)buf;
+  *out = fb;
+  return CBV2_OK;
+}
+
+int64_t cbv2_filter_batch_pairs(const cbv2_filter_batch* fb) { return fb ? fb->pairs : -1; }
+
+int64_t cbv2_filter_batch_max_count(const cbv2_filter_batch* fb) { return fb ? fb->max_m : -1; }
+
+int cbv2_filter_batch_destroy(cbv2_filter_batch* fb) {
+  delete fb;
+  return CBV2_OK;
+}
+
+size_t cbv2_search_filtered_batch_workspace_size(const cbv2_index* ix, const cbv2_filter_batch* fb, int32_t B,
+                                                 int32_t lq, int32_t k, int32_t scorer) {
+  if (!ix || !fb || B < 1 || lq < 1 || k < 1) return 0;
+  return filter_batch_plan(ix, fb, B, lq, scorer).total;
+}
+
+int cbv2_search_filtered_batch(cbv2_index* ix, const cbv2_filter_batch* fb, int32_t scorer, const void* Q,
+                               int32_t q_dtype, int32_t B, int32_t lq, int32_t k, void* ws, size_t ws_bytes,
+                               float* out_scores, int32_t* out_ids, void* stream) {
+  CBV2_REQUIRE(fb != nullptr, "null filter batch");
+  CBV2_REQUIRE(ix != nullptr, "null index");
+  const bool faithful = scorer == CBV2_SCORER_MAXSIM && q_dtype == CBV2_DTYPE_F32 && ix->resid != nullptr;
+  if (faithful) {
+    CBV2_REQUIRE(Q != nullptr && aligned16(Q), "query pointer must be non-null and 16-byte aligned");
+    CBV2_REQUIRE(B >= 1 && B <= 65535, "B must be in [1, 65535] (got %d)", B);
+    CBV2_REQUIRE(lq >= 1 && lq <= kLqMax, "lq must be in [1, %d] (got %d)", kLqMax, lq);
+  } else if (int rc = check_query(ix, scorer, Q, q_dtype, B, lq)) {
+    return rc;
+  }
+  CBV2_REQUIRE(fb->n == ix->n && fb->id_base == ix->id_base && fb->device == ix->device,
+               "the filter batch was created for another index (n %lld / %lld, id_base %lld / %lld, device %d / %d)",
+               (long long)fb->n, (long long)ix->n, (long long)fb->id_base, (long long)ix->id_base, fb->device,
+               ix->device);
+  CBV2_REQUIRE(B == fb->B, "the filter batch holds %d queries, the call %d", fb->B, B);
+  CBV2_REQUIRE(k >= 1, "k must be >= 1 (got %d)", k);
+  CBV2_REQUIRE(out_scores && out_ids, "null outputs");
+  const FilterPlan p = filter_batch_plan(ix, fb, B, lq, scorer);
+  CBV2_REQUIRE(ws != nullptr && ws_bytes >= p.total && aligned16(ws), "workspace too small or misaligned (%zu < %zu)",
+               ws_bytes, p.total);
+  DeviceGuard dg(ix->device);
+  if (!dg.ok) return fail(CBV2_EHIP, "cannot select device %d", ix->device);
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t M = fb->max_m;
+  if (M == 0) return topk_impl_empty(B, k, out_scores, out_ids, st);   // every row empty: padding only, no scan
+  int* ctr = (int*)ws;
+  float* row = (float*)((uint8_t*)ws + p.off_row);
+  int32_t* cand = (int32_t*)((uint8_t*)ws + p.off_cand);
+  float* dense = (float*)((uint8_t*)ws + p.off_dense);
+  const unsigned gy = (unsigned)std::min(B, 65535);
+  const unsigned gx = (unsigned)std::min<int64_t>((M + 255) / 256, 4096);
+  int rc;
+  F32Ws w;
+  if (faithful) {
+    f32_ws_layout(ix, CBV2_F32_SCORE, B, lq, 0, (uint8_t*)ws + p.off_f32, &w);
+    if ((rc = split_queries(ix, (const float*)Q, B, lq, &w, st))) return rc;
+  }
+  if (p.subset) {
+    hipLaunchKernelGGL(fb_prepare_kernel, dim3(gx, gy), dim3(256), 0, st, fb->table, B, M,
+                       faithful ? cand : (int32_t*)nullptr, row);
+    if ((rc = launch_check("fb_prepare_kernel"))) return rc;
+    rc = faithful ? rescore_ragged(ix, fb, &w, B, lq, cand, row, M, st)
+                  : launch_stream_ragged(ix, fb, (const uint16_t*)Q, B, lq, row, M, st);
+    if (rc) return rc;
+  } else {
+    rc = faithful ? launch_rescore(ix, &w, B, lq, nullptr, nullptr, ix->n, 0, dense, ix->n, st)
+                  : score_impl(ix, scorer, Q, B, lq, dense, ix->n, st, ctr);
+    if (rc) return rc;
+    hipLaunchKernelGGL(fb_gather_kernel, dim3(gx, gy), dim3(256), 0, st, dense, ix->n, fb->table, B, M, row);
+    if ((rc = launch_check("fb_gather_kernel"))) return rc;
+  }
+  // the compact rows' top-k over the common stride (positions: id_base 0), then positions -> global ids
+  rc = topk_impl(row, B, M, M, k, 0, (uint8_t*)ws + p.off_tk, p.tk_bytes, out_scores, out_ids, st, ix->device);
+  if (rc) return rc;
+  const int64_t total = (int64_t)B * k;
+  hipLaunchKernelGGL(fb_map_ids_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, out_ids, B, k,
+                     fb->table, fb->id_base);
+  return launch_check("fb_map_ids_kernel");
+}
+
 int cbv2_index_set_option(cbv2_index* ix, int32_t option, int64_t value) {
   CBV2_REQUIRE(ix != nullptr, "null index");
   switch (option) {
@@ -7744,6 +8030,10 @@ int cbv2_index_set_option(cbv2_index* ix, int32_t option, int64_t value) {
     case CBV2_OPT_FILTER_PATH:
       if (value < 0 || value > 2) return fail(CBV2_EINVAL, "filter path must be 0 (automatic), 1 (subset) or 2 (dense)");
       ix->filter_path = (int)value;
+      return CBV2_OK;
+    case CBV2_OPT_FILTER_BATCH_CHUNK_DOCS:
+      if (value < 0 || value > 0x7fffffffLL) return fail(CBV2_EINVAL, "filter batch chunk docs must be in [0, 2^31)");
+      ix->filter_batch_chunk_docs = value;
       return CBV2_OK;
     case CBV2_OPT_RESCORE_GRID:
       if (value < 0 || value > 65535) return fail(CBV2_EINVAL, "rescore grid must be in [0, 65535]");

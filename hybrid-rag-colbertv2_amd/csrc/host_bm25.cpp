@@ -137,11 +137,15 @@ extern "C" int cbv2_bm25_destroy(cbv2_bm25* ix) {
 }
 
 static void search_range(const cbv2_bm25* ix, const int32_t* q_terms, const int64_t* q_offsets, int32_t b0,
-                         int32_t b1, int32_t k, const uint32_t* allow, int32_t* out_ids, float* out_scores) {
+                         int32_t b1, int32_t k, const uint32_t* allow_all, const uint32_t* const* allows,
+                         int32_t* out_ids, float* out_scores) {
+  // one bitmap for the whole call (allow_all), or one per query (allows[b]; a null entry = unfiltered)
+  const uint32_t* allow = allow_all;
   auto allowed = [&](int64_t d) { return allow == nullptr || ((allow[d >> 5] >> (d & 31)) & 1u) != 0u; };
   std::vector<float> acc((size_t)ix->n_docs, 0.0f);
   std::vector<int32_t> touched, terms, order;
   for (int32_t b = b0; b < b1; ++b) {
+    if (allows != nullptr) allow = allows[b];
     terms.assign(q_terms + q_offsets[b], q_terms + q_offsets[b + 1]);
     touched.clear();
     for (int32_t t : terms) {
@@ -185,16 +189,16 @@ static void search_range(const cbv2_bm25* ix, const int32_t* q_terms, const int6
   }
 }
 
-extern "C" int cbv2_bm25_search_filtered(const cbv2_bm25* ix, const int32_t* q_terms, const int64_t* q_offsets,
-                                         int32_t B, int32_t k, int32_t n_threads, const uint32_t* allow,
-                                         int32_t* out_ids, float* out_scores) {
+static int search_pool(const cbv2_bm25* ix, const int32_t* q_terms, const int64_t* q_offsets, int32_t B, int32_t k,
+                       int32_t n_threads, const uint32_t* allow, const uint32_t* const* allows, int32_t* out_ids,
+                       float* out_scores) {
   if (!ix) return cbv2_set_error(CBV2_EINVAL, "null bm25 index");
   if (B < 0 || k < 1 || (B > 0 && (!q_offsets || !out_ids))) return cbv2_set_error(CBV2_EINVAL, "bad search arguments");
   if (B == 0) return CBV2_OK;
   int32_t T = n_threads > 0 ? n_threads : (int32_t)std::min<unsigned>(16u, std::max(1u, std::thread::hardware_concurrency()));
   if (T > B) T = B;
   if (T <= 1) {
-    search_range(ix, q_terms, q_offsets, 0, B, k, allow, out_ids, out_scores);
+    search_range(ix, q_terms, q_offsets, 0, B, k, allow, allows, out_ids, out_scores);
     return CBV2_OK;
   }
   std::vector<std::thread> pool;
@@ -202,10 +206,23 @@ extern "C" int cbv2_bm25_search_filtered(const cbv2_bm25* ix, const int32_t* q_t
   for (int32_t t = 0; t < T; ++t) {
     const int32_t b0 = t * per, b1 = std::min(B, b0 + per);
     if (b0 >= b1) break;
-    pool.emplace_back(search_range, ix, q_terms, q_offsets, b0, b1, k, allow, out_ids, out_scores);
+    pool.emplace_back(search_range, ix, q_terms, q_offsets, b0, b1, k, allow, allows, out_ids, out_scores);
   }
   for (auto& th : pool) th.join();
   return CBV2_OK;
+}
+
+extern "C" int cbv2_bm25_search_filtered(const cbv2_bm25* ix, const int32_t* q_terms, const int64_t* q_offsets,
+                                         int32_t B, int32_t k, int32_t n_threads, const uint32_t* allow,
+                                         int32_t* out_ids, float* out_scores) {
+  return search_pool(ix, q_terms, q_offsets, B, k, n_threads, allow, nullptr, out_ids, out_scores);
+}
+
+extern "C" int cbv2_bm25_search_filtered_batch(const cbv2_bm25* ix, const int32_t* q_terms, const int64_t* q_offsets,
+                                               int32_t B, int32_t k, int32_t n_threads,
+                                               const uint32_t* const* allows, int32_t* out_ids, float* out_scores) {
+  if (B > 0 && !allows) return cbv2_set_error(CBV2_EINVAL, "null per-query bitmap array");
+  return search_pool(ix, q_terms, q_offsets, B, k, n_threads, nullptr, allows, out_ids, out_scores);
 }
 
 extern "C" int cbv2_bm25_search(const cbv2_bm25* ix, const int32_t* q_terms, const int64_t* q_offsets, int32_t B,

@@ -268,7 +268,8 @@ class HybridRetriever:
         return final
 
     # ------------------------------------------------------------------ batched path
-    def retrieve_batch(self, Q: torch.Tensor, bm25_ids: np.ndarray, top_k_final: Optional[int] = None, filter=None):
+    def retrieve_batch(self, Q: torch.Tensor, bm25_ids: np.ndarray, top_k_final: Optional[int] = None, filter=None,
+                       filters=None):
         """All three stages for B query embeddings at once (the benchmark step).
 
         Q [B, lq, D] device; bm25_ids [B, kb] host int (stage-1 output) ->
@@ -277,11 +278,21 @@ class HybridRetriever:
         chunks; ``bm25_ids`` must come from a stage 1 under the same filter
         (``HostBM25.retrieve(allow=)``).  Filtered batches take the separate
         calls (search, host fusion, rerank), not the one-trip path.
+        ``filters`` (one ``DocFilter`` / chunk ids / ``None`` per query, or a
+        ``FilterBatch``): stage 2 ranks query b under entry b; row b of
+        ``bm25_ids`` must come from a stage 1 under the same entry
+        (``HostBM25.retrieve_batch``).  Stage 3 reranks the fused candidates,
+        which already come from filtered lists.
         """
         k_final = top_k_final or self.config.final_top_k
         retr = self.indexer.colbert_retriever
-        if filter is not None:
-            _, ids = retr.search_embeddings(Q, self.config.colbert_top_k, allowed_ids=filter)
+        if filter is not None and filters is not None:
+            raise ValueError("pass filter (one for the batch) or filters (one per query), not both")
+        if filter is not None or filters is not None:
+            if filters is not None:
+                _, ids = retr.search_embeddings(Q, self.config.colbert_top_k, filters=filters)
+            else:
+                _, ids = retr.search_embeddings(Q, self.config.colbert_top_k, allowed_ids=filter)
             cand = rrf_fuse(bm25_ids, ids.cpu().numpy(), rrf_k=self.config.rrf_k, C=self.config.fused_candidates)
             cand_d = torch.from_numpy(cand).to(retr.device)
             s, i, _ = retr.rerank_ids(Q, cand_d, k_final)

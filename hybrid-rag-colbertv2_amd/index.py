@@ -262,6 +262,50 @@ class DocFilter:
             pass
 
 
+class FilterBatch:
+    """One ``DocFilter`` per query of a call (cbv2_filter_batch_create): owns
+    the device table and the handle and keeps its filters alive.  Read-only;
+    reusable across searches of B = ``len(filters)`` queries.  Creating one
+    waits for the device once (the table's copy)."""
+
+    def __init__(self, index: "ColbertIndex", filters: Sequence[DocFilter]):
+        L = _lib.lib()
+        self.index = index
+        self.filters = list(filters)
+        B = len(self.filters)
+        if B < 1:
+            raise ValueError("a filter batch needs at least one filter")
+        for f in self.filters:
+            if not isinstance(f, DocFilter):
+                raise TypeError("filters must be DocFilter objects (ColbertIndex.filter)")
+            if not f._h.value:
+                raise ValueError("a filter of the batch is closed")
+        need = int(L.cbv2_filter_batch_bytes(B))
+        self._buf = torch.empty((max(need, 16),), dtype=torch.uint8, device=index.device)
+        arr = (ctypes.c_void_p * B)(*[f._h.value for f in self.filters])
+        h = ctypes.c_void_p()
+        _lib.check(L.cbv2_filter_batch_create(index._h, arr, B, self._buf.data_ptr(), self._buf.numel(),
+                                              _stream_ptr(index.device), ctypes.byref(h)))
+        self._h = h
+        self.B = B
+        self.pairs = int(L.cbv2_filter_batch_pairs(h))
+        self.max_count = int(L.cbv2_filter_batch_max_count(h))
+
+    def close(self) -> None:
+        if getattr(self, "_h", None) is not None and self._h.value:
+            _lib.lib().cbv2_filter_batch_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __len__(self):
+        return self.B
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class ColbertIndex:
     """One shard of the corpus resident in HBM, with a C handle borrowing it.
 
@@ -294,6 +338,8 @@ class ColbertIndex:
         self.means: Optional[torch.Tensor] = None
         self._ws: Optional[torch.Tensor] = None
         self._rr_ws: Optional[torch.Tensor] = None      # cbv2_rerank_ws workspace (small batches)
+        self._all_filter: Optional[DocFilter] = None    # all_docs_filter()'s cache
+        self._last_filter_batch: Optional[FilterBatch] = None
         h = ctypes.c_void_p()
         dev = self.device.index if self.device.index is not None else torch.cuda.current_device()
         if self.fp8:
@@ -659,13 +705,69 @@ class ColbertIndex:
                                           _stream_ptr(self.device)))
         return out_s, out_i
 
+    def all_docs_filter(self) -> DocFilter:
+        """The cached filter that allows every doc of the shard (a ``None``
+        entry of ``search(filters=...)``)."""
+        if self._all_filter is None:
+            self._all_filter = self.filter(mask=torch.ones(self.n, dtype=torch.bool))
+        return self._all_filter
+
+    def filter_batch(self, filters: Sequence[Optional[DocFilter]]) -> FilterBatch:
+        """A ``FilterBatch`` of this shard: one ``DocFilter`` (or ``None`` =
+        every doc) per query of a later ``search(Q, k, filters=batch)``."""
+        return FilterBatch(self, [self.all_docs_filter() if f is None else f for f in filters])
+
+    def _search_filtered_batch(self, Q: torch.Tensor, k: int, scorer: str, filters):
+        """Row b: the top-k of filters[b]'s docs (cbv2_search_filtered_batch; asynchronous)."""
+        k = int(k)
+        B = int(Q.shape[0]) if Q.dim() == 3 else 1
+        batch = filters if isinstance(filters, FilterBatch) else None
+        flts = batch.filters if batch is not None else list(filters)
+        if len(flts) != B:
+            raise ValueError(f"filters must hold one entry per query ({len(flts)} for {B} queries)")
+        if batch is None and all(f is flts[0] for f in flts) and flts[0] is not None:
+            return self._search_filtered(Q, k, scorer, flts[0])   # one filter for the whole call
+        if self._query_blocks(Q, scorer) is not None:   # long queries: the single-filter route, row by row
+            Q3 = Q if Q.dim() == 3 else Q[None]
+            rows = [self._search_filtered(Q3[b:b + 1], k, scorer, self.all_docs_filter() if f is None else f)
+                    for b, f in enumerate(flts)]
+            return torch.cat([r[0] for r in rows]), torch.cat([r[1] for r in rows])
+        if batch is None:
+            batch = self.filter_batch(flts)
+        if not batch._h.value:
+            raise ValueError("the filter batch is closed")
+        sid = self._scorer(scorer)
+        _keep, qptr, qdt, B, lq = self._prep_query(Q, scorer)
+        L = _lib.lib()
+        need = int(L.cbv2_search_filtered_batch_workspace_size(self._h, batch._h, B, lq, k, sid))
+        if self._ws is None or self._ws.numel() * 4 < need:
+            self._ws = torch.empty(((need + 3) // 4,), dtype=torch.float32, device=self.device)
+        out_s = torch.empty((B, k), dtype=torch.float32, device=self.device)
+        out_i = torch.empty((B, k), dtype=torch.int32, device=self.device)
+        _lib.check(L.cbv2_search_filtered_batch(self._h, batch._h, sid, qptr, qdt, B, lq, k, self._ws.data_ptr(),
+                                                self._ws.numel() * 4, out_s.data_ptr(), out_i.data_ptr(),
+                                                _stream_ptr(self.device)))
+        # the launches borrow the batch's table and lists: keep them until the next search replaces them
+        self._last_filter_batch = batch
+        return out_s, out_i
+
     def search(self, Q: torch.Tensor, k: int, scorer: str = "maxsim",
-               lb_reduce=None, filter: Optional[DocFilter] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+               lb_reduce=None, filter: Optional[DocFilter] = None,
+               filters=None) -> Tuple[torch.Tensor, torch.Tensor]:
         """Top-k over the shard: (f32 [B, k] scores, int32 [B, k] global ids), -inf/-1 padded.
 
         ``filter`` (a ``DocFilter`` of this index, ``ColbertIndex.filter``): the
         top-k of the allowed docs only, their scores those of the unfiltered
         scorer bit for bit; not combinable with ``lb_reduce``.
+
+        ``filters`` (a sequence of B ``DocFilter`` / ``None`` entries, or a
+        ``FilterBatch`` from ``filter_batch``): per-query filters, row b being
+        what ``filter=filters[b]`` returns for query b alone; ``None`` allows
+        every doc.  A sequence of one and the same object takes the
+        single-filter path.  Not combinable with ``filter`` or ``lb_reduce``.
+        MaxSim queries of more than 32 tokens do not take the batch call: each
+        row runs the single-filter long-query route (a full score of the shard
+        per 32-token block, a column gather and a row top-k), B times over.
 
         ``lb_reduce`` (fp32-faithful index, sharded corpus): called with the
         exact faithful scores of this shard's bf16 top-k (device f32 [B, k]);
@@ -674,6 +776,12 @@ class ColbertIndex:
         rescores only the docs that can reach the global top-k and returns its
         part of it, which the merge completes (cbv2_search_f32_begin /
         _finish)."""
+        if filters is not None:
+            if filter is not None:
+                raise ValueError("pass filter (one for the call) or filters (one per query), not both")
+            if lb_reduce is not None:
+                raise ValueError("filters cannot be combined with lb_reduce (sharded faithful filtering is out of scope)")
+            return self._search_filtered_batch(Q, k, scorer, filters)
         if filter is not None:
             if lb_reduce is not None:
                 raise ValueError("filter cannot be combined with lb_reduce (sharded faithful filtering is out of scope)")

@@ -27,7 +27,7 @@ import torch
 
 from .config import RAGConfig
 from .encoder import encode, load_local_encoder
-from .index import ColbertIndex, DocFilter, IndexBuilder, select_topk
+from .index import ColbertIndex, DocFilter, FilterBatch, IndexBuilder, select_topk
 
 
 class JinaColBERTRetriever:
@@ -196,9 +196,17 @@ class JinaColBERTRetriever:
         return [{"document_id": int(i), "score": float(s), "text": self.corpus[i] if self.corpus else None}
                 for s, i in zip(scores, ids)]
 
-    def search_embeddings(self, Q: torch.Tensor, k: int, allowed_ids=None):
+    def search_embeddings(self, Q: torch.Tensor, k: int, allowed_ids=None, filters=None):
         """Batched stage 2: Q [B, lq, D] -> device (scores [B, k], global ids [B, k]);
-        ``allowed_ids`` as in ``search`` (slots past the allowed count: -inf / -1)."""
+        ``allowed_ids`` as in ``search`` (slots past the allowed count: -inf / -1).
+        ``filters``: one entry per query (a ``DocFilter``, chunk ids, or ``None``
+        for every chunk), or a ``FilterBatch``: row b ranks only entry b's chunks."""
+        if filters is not None:
+            if allowed_ids is not None:
+                raise ValueError("pass allowed_ids (one filter for the call) or filters (one per query), not both")
+            if not isinstance(filters, FilterBatch):
+                filters = [self._as_filter(f) for f in filters]
+            return self.corpus_embeddings.search(Q, k, scorer=self.scorer, filters=filters)
         if allowed_ids is None:
             return self.corpus_embeddings.search(Q, k, scorer=self.scorer)
         return self.corpus_embeddings.search(Q, k, scorer=self.scorer, filter=self._as_filter(allowed_ids))

@@ -38,9 +38,17 @@
  *      - with cbv2_index_time_scans enabled, launches on a capturing stream
  *        are not timed: cbv2_index_scan_times / _band_times report the eager
  *        launches only, never a graph's replays.
+ *    The list above has one more member, cbv2_search_filtered_batch (the
+ *    per-query form of cbv2_search_filtered; the filter batch created before
+ *    the capture): it may be issued on a capturing stream, every replay
+ *    recomputes it from the buffers' contents at replay time and
+ *    re-initialises what it uses in the caller's workspace, like the searches
+ *    above (tests/test_gpu_filter_batch.py replays it over a poisoned
+ *    workspace and poisoned outputs).
  *    Outside the list, not to be captured: cbv2_retrieve_* (pooled mapped buffers, a second stream
  *    and host polling), the sharded and loopback calls, cbv2_filter_create
- *    (waits for its count), the index-file, writer and cbv2_hbm_* calls, and
+ *    (waits for its count), cbv2_filter_batch_create (copies its table from
+ *    the host and waits for it), the index-file, writer and cbv2_hbm_* calls, and
  *    cbv2_index_build_means.
  *  - Return 0 on success, a negative CBV2_E* code on error; the message is in
  *    the thread-local `cbv2_last_error()`.  Arguments are validated on the host
@@ -217,6 +225,10 @@ int cbv2_index_scan_clock(cbv2_index* index, int64_t* out4, int32_t reset);
  *                        dense path: DESIGN.md 3.8), 1 the subset path where
  *                        supported, 2 the dense path (score every doc, gather
  *                        the allowed columns).  Identical results.
+ *  CBV2_OPT_FILTER_BATCH_CHUNK_DOCS  docs per work item of the per-query
+ *                        filters' ragged scan (0: automatic, from the batch's
+ *                        pair count and the CU count; > 0: for tests).  Read
+ *                        by cbv2_filter_batch_create.  Identical results.
  * cbv2_index_last_scan_plan: the work split of this handle's latest scan
  * launch: {workgroups, static chunk docs, static docs, dynamic tail 0/1}.
  * Thread safety: one handle may be used from several host threads and
@@ -236,6 +248,7 @@ int cbv2_index_scan_clock(cbv2_index* index, int64_t* out4, int32_t reset);
 #define CBV2_OPT_P1_COLLECT_FUSED 12
 #define CBV2_OPT_FOLD_KEYS 13
 #define CBV2_OPT_FILTER_PATH 14
+#define CBV2_OPT_FILTER_BATCH_CHUNK_DOCS 15
 int cbv2_index_set_option(cbv2_index* index, int32_t option, int64_t value);
 int cbv2_index_last_scan_plan(const cbv2_index* index, int64_t* out4);
 /* Per-query workgroup lists a cbv2_search of (B, k, scorer) keeps with the
@@ -300,7 +313,8 @@ int cbv2_search(cbv2_index* index, int32_t scorer, const void* Q, int32_t q_dtyp
  * document, one tenant, a metadata predicate).  A filter is a bitmap over the
  * shard's LOCAL docs: ceil(n / 32) uint32 words on the device, doc i allowed
  * when bit i & 31 of word i >> 5 is set; bits at positions >= n are ignored.
- * One filter serves a whole call (no per-query filters).
+ * One filter serves a whole cbv2_search_filtered call; one filter per query:
+ * cbv2_search_filtered_batch below.
  *  - cbv2_filter_create compacts the bitmap into the ascending list of the
  *    allowed local ids (popcount per word, prefix sum over the words, scatter)
  *    in `buf`, a caller-owned DEVICE buffer of cbv2_filter_bytes(n) bytes
@@ -344,6 +358,61 @@ size_t cbv2_search_filtered_workspace_size(const cbv2_index* index, const cbv2_f
 int cbv2_search_filtered(cbv2_index* index, const cbv2_filter* filter, int32_t scorer, const void* Q, int32_t q_dtype,
                          int32_t B, int32_t lq, int32_t k, void* workspace, size_t workspace_bytes,
                          float* out_scores, int32_t* out_ids, void* stream);
+
+/* Per-query filters: one filtered search for a batch whose queries each have
+ * their own allowed set (256 users, each asking about their own document).
+ * A filter batch assigns one existing cbv2_filter to each of the B queries of
+ * a call; handles may repeat.
+ *  - cbv2_filter_batch_create checks every filter against the index (n,
+ *    id_base, device; a null entry or a mismatch is CBV2_EINVAL, nothing is
+ *    launched) and writes the per-row table -- the exclusive prefix of the
+ *    rows' work items [B + 1], the counts m_b [B] and the lists' addresses
+ *    [B], 4 B + 1 int32 words -- into `buf`, a caller-owned DEVICE buffer of
+ *    cbv2_filter_batch_bytes(B) bytes (16-B aligned).  `per_query` is a HOST
+ *    array read during the call only.  It returns when the table is on the
+ *    device (it waits on `stream`): NOT capturable.  The batch borrows `buf`
+ *    and the filters until cbv2_filter_batch_destroy, is read-only afterwards
+ *    and may be shared across streams.  The ragged scan's docs per work item
+ *    are fixed here (CBV2_OPT_FILTER_BATCH_CHUNK_DOCS).
+ *  - cbv2_search_filtered_batch: row b is what cbv2_search_filtered(index,
+ *    per_query[b], ..., Q + b, B = 1, ...) returns, bit for bit: the top-k of
+ *    filter b's docs, score descending then id ascending, global ids; slots
+ *    past min(k, m_b) hold -inf / -1 (a row with m_b == 0 is all padding); an
+ *    allowed doc with doclens == 0 scores -inf, keeps its id and ranks after
+ *    every finite score.  Query types, scorers and index kinds: those of
+ *    cbv2_search_filtered.  B must equal the batch's B (CBV2_EINVAL).  If
+ *    every m_b is 0 no scan is launched.  Asynchronous and capturable, no host
+ *    round trip.  MaxSim queries hold at most 32 tokens here, as in every
+ *    search call (longer queries: the caller sums the scores of 32-token
+ *    blocks; the Python layer then serves per-query filters row by row).  Paths (CBV2_OPT_FILTER_PATH; the automatic rule of
+ *    cbv2_search_filtered applied to M = the largest m_b):
+ *    subset, bf16 -- ONE launch of the ragged streaming scan for all rows: a
+ *      wave's work item is (row b, chunk of row b's list), found by a search
+ *      of the table's prefix; each (query, allowed doc) pair is streamed and
+ *      scored on its own (queries sharing a filter share no loads);
+ *    subset, faithful -- the lists gathered into a candidate matrix [B][M],
+ *      then one faithful score per (query, allowed doc), count[b] = m_b;
+ *    dense -- the full scorer into [B][n], then a ragged gather.
+ *    All end in the row top-k over compact rows of stride M whose columns past
+ *    m_b hold -inf, and a map of positions to id_base + list_b[pos] (-1 at or
+ *    past m_b).  Workspace (16-B aligned, one per stream), with r = round up
+ *    to 256 B:  counters + r(top-k workspace of (B, M)) + r(4 B M) for the
+ *    rows + [faithful subset: r(4 B M) for the candidates] + [dense:
+ *    r(4 B n)] + [faithful index: the query split of cbv2_score_f32];
+ *    cbv2_search_filtered_batch_workspace_size is authoritative and is
+ *    computed with the options the search will run under.                  */
+typedef struct cbv2_filter_batch cbv2_filter_batch;
+size_t cbv2_filter_batch_bytes(int32_t B);
+int cbv2_filter_batch_create(const cbv2_index* index, const cbv2_filter* const* per_query, int32_t B, void* buf,
+                             size_t buf_bytes, void* stream, cbv2_filter_batch** out);
+int64_t cbv2_filter_batch_pairs(const cbv2_filter_batch* fb);
+int64_t cbv2_filter_batch_max_count(const cbv2_filter_batch* fb);
+int cbv2_filter_batch_destroy(cbv2_filter_batch* fb);
+size_t cbv2_search_filtered_batch_workspace_size(const cbv2_index* index, const cbv2_filter_batch* fb, int32_t B,
+                                                 int32_t lq, int32_t k, int32_t scorer);
+int cbv2_search_filtered_batch(cbv2_index* index, const cbv2_filter_batch* fb, int32_t scorer, const void* Q,
+                               int32_t q_dtype, int32_t B, int32_t lq, int32_t k, void* workspace,
+                               size_t workspace_bytes, float* out_scores, int32_t* out_ids, void* stream);
 
 /* cbv2_rerank — JinaColBERTRetriever.rerank (local_rag_complete.py:779-800)
  * without re-encoding: the C candidate docs of each query are GATHERED from
@@ -503,6 +572,13 @@ int cbv2_bm25_search(const cbv2_bm25* index, const int32_t* q_terms, const int64
 int cbv2_bm25_search_filtered(const cbv2_bm25* index, const int32_t* q_terms, const int64_t* q_offsets, int32_t B,
                               int32_t k, int32_t n_threads, const uint32_t* allow, int32_t* out_ids,
                               float* out_scores);
+/* cbv2_bm25_search_filtered_batch: query b under its own bitmap allows[b]
+ * (HOST array [B] of HOST bitmaps; a NULL entry = unfiltered).  Each row equals
+ * cbv2_bm25_search_filtered on that query alone, ids, score bits and the
+ * zero-score padding rule included.                                        */
+int cbv2_bm25_search_filtered_batch(const cbv2_bm25* index, const int32_t* q_terms, const int64_t* q_offsets, int32_t B,
+                                    int32_t k, int32_t n_threads, const uint32_t* const* allows, int32_t* out_ids,
+                                    float* out_scores);
 /* Sharded BM25 (no reference counterpart): a rank indexes
  * only its doc range [id_base, id_base + n_docs) but with the GLOBAL
  * statistics (n_global docs, total_global tokens, df_global [vocab] from an
