@@ -53,6 +53,13 @@
  *  - Return 0 on success, a negative CBV2_E* code on error; the message is in
  *    the thread-local `cbv2_last_error()`.  Arguments are validated on the host
  *    BEFORE any launch: a call that returns an error has launched nothing.
+ *  - Bounds.  No call writes outside the extents stated in this file (an
+ *    output [B][k], a workspace of exactly its *_workspace_size bytes, a
+ *    filter `buf` of exactly cbv2_filter_bytes(n) bytes), no value outside
+ *    them influences a result (doc n, doclens[n], bitmap bits at or past n,
+ *    candidate C), and inputs are never written.  Pinned by
+ *    tests/test_gpu_bounds.py, which runs every device entry point inside
+ *    guard bands.
  *  - Ranking ties are broken deterministically: score descending, then the
  *    lower index in the scored list (doc id for search, candidate position for
  *    rerank).  The reference's torch.topk / argsort (local_rag_complete.py:767,
