@@ -151,13 +151,30 @@ struct MappedBuf {
 // layout may poll words where such data lies: a small counter as the tag
 // could equal a stale doc id in a word's high half and pass the check with
 // the other id as its value (round-6 soak, tools/stress_onetrip.py: 3-5 in
-// 120k calls).  No id, position or MaxSim score has the top bit set with the
-// rest below 2^31 - 1 (-0.0 is counter 0, never used; -inf and -1 sit at
-// counters no process reaches), so a stale word never passes for a call's.
+// 120k calls).  The top bit keeps ids >= 0, positions and positive scores
+// from ever equalling a tag, but not every stale value: -1 padding
+// (0xFFFFFFFF) is counter 0x7FFFFFFF's tag, -inf (0xFF800000) counter
+// 0x7F800000's, and any negative score some counter's -- and next_tag
+// reaches every counter.  So the tag alone proves nothing about a stale
+// word: every word a call polls is zeroed (clear_words; tag 0 is never a
+// call's) before the launch that writes it or the host publishes it, while
+// the buffer is this call's alone (take_mapped hands it out after its last
+// reader).  A polled word then holds 0 or this call's own value.
+thread_local uint32_t t_lab_tag = 0;   // lab knob (cbv2_set_tag_lab): the next call's counter, 0 = none
 uint32_t next_tag(MappedBuf& b) {
+  if (t_lab_tag != 0) {
+    b.seq = (t_lab_tag - 1) & 0x7fffffffu;
+    t_lab_tag = 0;
+  }
   b.seq = (b.seq + 1) & 0x7fffffffu;
   if (b.seq == 0) b.seq = 1;
   return 0x80000000u | b.seq;
+}
+// Zeroes n tagged words of a mapped buffer before their writer is launched.
+void clear_words(uint64_t* w, size_t n) {
+  volatile uint64_t* v = w;
+  for (size_t i = 0; i < n; ++i) v[i] = 0;
+  std::atomic_thread_fence(std::memory_order_seq_cst);
 }
 struct MappedPool {
   std::mutex mu;
@@ -552,6 +569,9 @@ void cbv2_set_wait_lab(int64_t ticks, int32_t publish_delay_us) {
   cbv2_set_wait_ticks(ticks);
   t_lab_publish_delay_us = publish_delay_us;
 }
+// Lab knob (tests, this thread): the counter ([1, 0x7FFFFFFF]) of the next
+// call this thread begins on a mapped buffer; the buffer counts on from it.
+void cbv2_set_tag_lab(uint32_t counter) { t_lab_tag = counter & 0x7fffffffu; }
 void cbv2_set_host_rerank(int32_t on) { g_host_rerank = on; }
 void cbv2_set_prearm(int32_t on) { g_prearm = on; }
 void cbv2_set_begin_probe(int32_t on) { t_begin_probe = on; }
@@ -623,6 +643,9 @@ int cbv2_retrieve_begin(cbv2_index* ix, cbv2_comm* c, const void* Q, int32_t q_d
     for (int32_t b = 0; b < B; ++b) fl[b] = 0;
     std::atomic_thread_fence(std::memory_order_seq_cst);
   }
+  // ... and so may the stage-2 id (and score) words finish polls (B <=
+  // kSpinMaxB; larger batches wait for the stream): zeroed before the search
+  if (mapped && B <= kSpinMaxB) clear_words((uint64_t*)pd.mb.h, (size_t)B * k * (host_rr ? 2 : 1));
   cbv2_set_ids_mirror(mapped ? pd.mb.d : nullptr, pd.seq, host_rr ? (int64_t)B * k : 0);
   pd.ready_seq = host_rr ? next_ready_seq() : 0;
   cbv2_set_split_ready_begin(pd.ready_seq, host_rr ? (uint64_t*)pd.mb.d + ready_word_off(pd.mb, B) : nullptr);
@@ -678,7 +701,9 @@ int host_rerank(cbv2_index* ix, Kind kd, const void* Q, int32_t B, int32_t lq, i
   int rc = CBV2_OK;
   hipStream_t pre = st;   // the stream the stage-1 prescore went to
   // 1. stage 1's prescore: the rerank's raw scores of the whole stage-1 list
+  gate[0] = gate[1] = 0;   // (an earlier call's gate words, should a counter come round again)
   if (kb > 0) {
+    clear_words(lxw, Bkb);   // polled below: no earlier call's data passes for a prescore
     std::memcpy(lxi, lex_ids, Bkb * 4);
     cbv2_set_raw_mirror(dev(lxw), pd.seq);
     const int32_t* lxi_d = (const int32_t*)dev(lxi);
@@ -712,6 +737,8 @@ int host_rerank(cbv2_index* ix, Kind kd, const void* Q, int32_t B, int32_t lq, i
     if (!rc && !used) rc = err(CBV2_ESTATE, "stage-1 prescore without host words");
   }
   // 2. the device outputs: a copy launched now, polling the final words
+  //    (zeroed first: the copy takes nothing but what this call publishes)
+  clear_words(fw, (size_t)3 * B * fk);
   if (!rc) rc = cbv2_host_result_copy(dev(fw), pd.seq, B, fk, out_scores, out_ids, out_pos, dev(gate), st);
   const bool copy_armed = rc == CBV2_OK;
   mark_mapped(pd.mb, st);   // every reader of the buffer is enqueued
@@ -911,8 +938,8 @@ int finish_impl(cbv2_index* ix, cbv2_comm* c, const void* Q, int32_t q_dtype, in
   // host results: the final select's words after the candidate words, when the
   // buffer holds them (pool buffers are >= 64 KiB)
   const size_t fin_words = (size_t)3 * B * final_k;
-  uint64_t* const fw = mapped && host_s && ((size_t)B * (2 * (size_t)k + C) + fin_words) * 8 <= pd.mb.bytes
-                           ? cw + (size_t)B * C : nullptr;
+  uint64_t* const fw = mapped && host_s && (size_t)B * (2 * (size_t)k + C) + fin_words <= gate_word_off(pd.mb, B)
+                           ? cw + (size_t)B * C : nullptr;   // (below the wait gate and the ready flags)
   uint64_t* const fwd = fw ? (uint64_t*)pd.mb.d + (size_t)B * (2 * (size_t)k + C) : nullptr;
   bool fin_used = false;
   rc = CBV2_OK;
@@ -921,7 +948,13 @@ int finish_impl(cbv2_index* ix, cbv2_comm* c, const void* Q, int32_t q_dtype, in
   mark(1);
   bool armed = false;
   uint64_t* const gate = mapped ? (uint64_t*)pd.mb.h + gate_word_off(pd.mb, B) : nullptr;
+  // the words polled from here on, zeroed before the launch that writes or
+  // polls them: the final words (the host polls them), the wait gate and the
+  // candidate words (the pre-armed rerank polls them)
+  if (fw) clear_words(fw, fin_words);
   if (!rc && prearm) {
+    gate[0] = gate[1] = 0;
+    clear_words(cw, (size_t)B * C);
     cbv2_set_cand_tagged(cwd, pd.seq, (uint64_t*)pd.mb.d + gate_word_off(pd.mb, B));
     if (fwd) cbv2_set_final_mirror(fwd, pd.seq, final_k);
     rc = rerank_call(ix, c, kd, Q, B, lq, k, kb, L, L.cand, C, final_k, out_scores, out_ids, out_pos, st);
