@@ -24,7 +24,10 @@ LIB = os.path.join(PKG, "libcolbert_mi355x.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -fno-honor-nans: lets fmaxf on MFMA results lower to bare v_max3_f32 (no
 # canonicalising v_max per operand); the path never feeds NaNs on purpose.
-FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-fno-honor-nans", "-pthread",
+# The .hip sources (the library's and the lab tools') take their kernel configs
+# as class-type template arguments: C++20.  The host .cpp files stay valid C++17.
+STD = "-std=c++20"
+FLAGS = ["--offload-arch=gfx950", "-O3", STD, "-fPIC", "-shared", "-fno-honor-nans", "-pthread",
          "-Wall", "-Wno-unused-function"]
 _STAMP_RE = re.compile(rb"cbv2-build-stamp:([0-9a-f]{16}|unstamped)")
 

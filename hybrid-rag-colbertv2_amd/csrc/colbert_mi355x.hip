@@ -928,16 +928,31 @@ __device__ __forceinline__ void clock_probe(uint64_t* p, bool end) {
   atomicAdd(reinterpret_cast<unsigned long long*>(p) + (end ? 3 : 2), 1ull);
 }
 
-template <int WAVES, int QW, int D = 2, int NBUF = 3, bool STAMPS = false, int TPI = 32, int OCC = 2,
-          bool SPREAD = false, int FK = 0, bool SPLITLOAD = false, bool ARRIVE = false, int PROBE = 0, int LD = kLd,
-          int MORDER = 0, int AUX = 0, bool BMK = false, bool IDX = false>
-__global__ __launch_bounds__(WAVES * 64, OCC) void maxsim_scan16x4_kernel(
+// The kernel's shape, one template argument (equal values: one instantiation); the capitals above are its fields.
+struct Scan16x4Cfg {
+  int waves, qw;                 // waves per workgroup, queries per wave
+  int d = 2, nbuf = 3;           // fold distance of a chain's row max, ring depth
+  bool stamps = false;
+  int tpi = 32, occ = 2;         // tokens of 4 docs per iteration, launch-bounds occupancy
+  bool spread = false;
+  int fk = 0;                    // fused top-k key capacity (0: scores)
+  bool splitload = false, arrive = false;
+  int probe = 0, ld = kLd, morder = 0, aux = 0;   // (probe, morder: lab) token slots per doc
+  bool bmk = false, idx = false;
+};
+template <Scan16x4Cfg C>
+__global__ __launch_bounds__(C.waves * 64, C.occ) void maxsim_scan16x4_kernel(
     const uint8_t* __restrict__ tokens, const int32_t* __restrict__ doclens, int64_t n,
     const uint16_t* __restrict__ Q, int B, int lq, float* __restrict__ out, int64_t ld_out,
     int64_t chunk_docs, int64_t static_docs, int* __restrict__ task_ctr, int task_docs,
     uint64_t* __restrict__ stamps, int topk_k = 0, uint64_t* __restrict__ part = nullptr, int nslots = 0,
     int tail_slices = 1, uint32_t* __restrict__ bmk = nullptr, int64_t bmk_ld = 0, uint32_t* __restrict__ sbk = nullptr,
     int64_t sbk_ld = 0, const int32_t* __restrict__ ids = nullptr) {
+  // (static: an automatic constexpr is an alloca in the IR even when never read, and their order showed in the registers)
+  static constexpr int WAVES = C.waves, QW = C.qw, D = C.d, NBUF = C.nbuf, TPI = C.tpi, FK = C.fk, PROBE = C.probe, LD = C.ld,
+                MORDER = C.morder, AUX = C.aux;
+  static constexpr bool STAMPS = C.stamps, SPREAD = C.spread, SPLITLOAD = C.splitload, ARRIVE = C.arrive, BMK = C.bmk,
+                 IDX = C.idx;
   // IDX (the filtered search's subset scan): the n "docs" are the entries of
   // an ascending list of local doc ids; entry i is doc ids[i] (its tokens and
   // its length go through the list) and scores into column i of the compact
@@ -1492,13 +1507,19 @@ __device__ __forceinline__ int sload_len(const int32_t* p) {
 __host__ __device__ constexpr int64_t fb_off_count(int64_t B) { return B + 1; }       // int32 [B]: m_b
 __host__ __device__ constexpr int64_t fb_off_list(int64_t B) { return 2 * B + 1; }    // int32 [B][2]: list address, lo / hi
 __host__ __device__ constexpr int64_t fb_table_ints(int64_t B) { return 4 * B + 1; }  // (prefix: int32 [B + 1] at 0)
-template <int QW, int AUX, int WAVES = 4, int SLOTS = kStreamSlots, bool TW2 = false, bool PF = false,
-          bool IDX = false, bool RAG = false>
-__global__ __launch_bounds__(WAVES * 64, 1) void maxsim_scan_stream_kernel(
+struct StreamCfg {
+  int qw, aux;                          // queries per wave, the doc stream's cache policy (AUX above)
+  int waves = 4, slots = kStreamSlots;  // waves per workgroup, tile slots per wave
+  bool tw2 = false, pf = false, idx = false, rag = false;
+};
+template <StreamCfg C>
+__global__ __launch_bounds__(C.waves * 64, 1) void maxsim_scan_stream_kernel(
     const uint8_t* __restrict__ tokens, const int32_t* __restrict__ doclens, int64_t n_arg,
     const uint16_t* __restrict__ Q, int B, int lq, float* __restrict__ out, int64_t ld_out, int64_t chunk_docs,
     int ld, uint32_t* __restrict__ bm, int64_t bm_ld, uint32_t* __restrict__ sb, int64_t sb_ld,
     const int32_t* __restrict__ ids_arg = nullptr, const int32_t* __restrict__ rag = nullptr) {
+  static constexpr int QW = C.qw, AUX = C.aux, WAVES = C.waves, SLOTS = C.slots;
+  static constexpr bool TW2 = C.tw2, PF = C.pf, IDX = C.idx, RAG = C.rag;
   static_assert(!RAG || (IDX && QW == 1), "the ragged scan walks one list per query");
   __shared__ __attribute__((aligned(1024))) uint8_t smem[WAVES * SLOTS * 4096];
   const int lane = threadIdx.x & 63;
@@ -2196,15 +2217,25 @@ __device__ __forceinline__ void iter_f8x4_ragged(const uint8_t* buf, int lane, i
 // (with PAIR) issues pair p+1's second iteration after the first iteration of
 // pair p instead of right after the barrier (-0.3 %); SPLIT has only waves
 // 0 .. WAVES/2 - 1 issue the DMA pieces (+0.2 %, within noise, 4 VGPR spills).
-template <int WAVES, int QW, int D = 1, int NBUF = 3, int TPI = 32, bool PF = false, int OCC = 2,   // D = 2 spills at QW = 8
-          int FK = 0, int LD = kLd, bool PQS = false, bool PAIR = false, bool SPREAD2 = false, bool SPLIT = false,
-          bool QUAD = false, int PROBE = 0, int AUX = 0>
-__global__ __launch_bounds__(WAVES * 64, OCC) void maxsim_scan_f8x4_kernel(
+struct F8x4Cfg {
+  int waves, qw;                 // waves per workgroup, queries per wave
+  int d = 1, nbuf = 3, tpi = 32;   // fold distance, ring depth, tokens per iteration   // D = 2 spills at QW = 8
+  bool pf = false;               // the prefetch after each tile's first MFMA
+  int occ = 2, fk = 0, ld = kLd;   // launch-bounds occupancy, fused top-k key capacity, token slots per doc
+  bool pqs = false;              // the query scale bytes packed four per VGPR
+  bool pair = false, spread2 = false, split = false, quad = false;
+  int probe = 0, aux = 0;        // lab probe; the doc stream's cache policy (as maxsim_scan16x4_kernel's AUX)
+};
+template <F8x4Cfg C>
+__global__ __launch_bounds__(C.waves * 64, C.occ) void maxsim_scan_f8x4_kernel(
     const uint8_t* __restrict__ tokens, const uint8_t* __restrict__ tscales, const int32_t* __restrict__ doclens,
     int64_t n, const uint8_t* __restrict__ Qb, const uint8_t* __restrict__ Qs, int B, int lq,
     float* __restrict__ out, int64_t ld_out, int64_t chunk_docs, int64_t static_docs, int* __restrict__ task_ctr,
     int task_docs, int topk_k = 0, uint64_t* __restrict__ part = nullptr, int nslots = 0, int tail_slices = 1,
     uint64_t* __restrict__ clk = nullptr) {
+  static constexpr int WAVES = C.waves, QW = C.qw, D = C.d, NBUF = C.nbuf, TPI = C.tpi, FK = C.fk, LD = C.ld, PROBE = C.probe,
+                AUX = C.aux;
+  static constexpr bool PF = C.pf, PQS = C.pqs, PAIR = C.pair, SPREAD2 = C.spread2, SPLIT = C.split, QUAD = C.quad;
   if (clk != nullptr && threadIdx.x == 0) clock_probe(clk, false);   // the bench's clock probe (null otherwise)
   constexpr int QPB = WAVES * QW;
   constexpr int kIterBytes = 4 * TPI * kDim;                 // e4m3 bytes per iteration
@@ -2539,11 +2570,18 @@ constexpr int kF8SlotBytes = 2048 + 256;
 // (profiles/r03z_lab_f8_tw2.log: variant 10 = one tile per wait, 32 = TW2 at
 // 8 x 8, 33 = TW2 at 4 x 16): 1.25M docs B=1 3.320 -> 3.282 ms, B=2 3.178 ->
 // 3.155, 125k B=1 0.318 -> 0.316; at 4 x 16 B=2 and 125k lose (3.342 / 0.423).
-template <int QW, int AUX, int WAVES = 4, int SLOTS = 16, bool TW2 = true>
-__global__ __launch_bounds__(WAVES * 64, 1) void maxsim_scan_f8_stream_kernel(
+struct F8StreamCfg {
+  int qw, aux;                 // queries per wave, the doc stream's cache policy
+  int waves = 4, slots = 16;   // waves per workgroup, tile slots per wave
+  bool tw2 = true;             // TW2
+};
+template <F8StreamCfg C>
+__global__ __launch_bounds__(C.waves * 64, 1) void maxsim_scan_f8_stream_kernel(
     const uint8_t* __restrict__ tokens, const uint8_t* __restrict__ tscales, const int32_t* __restrict__ doclens,
     int64_t n, const uint8_t* __restrict__ Qb, const uint8_t* __restrict__ Qs, int B, int lq,
     float* __restrict__ out, int64_t ld_out, int64_t chunk_docs, int ld) {
+  static constexpr int QW = C.qw, AUX = C.aux, WAVES = C.waves, SLOTS = C.slots;
+  static constexpr bool TW2 = C.tw2;
   __shared__ __attribute__((aligned(1024))) uint8_t smem[WAVES * SLOTS * kF8SlotBytes];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -5977,17 +6015,24 @@ int pick_shape(const ShapeCost (&c)[N], int B) {
 constexpr ShapeCost kBf16Shapes[] = {
     {4, 4.6f, kScan16x4W4Q1}, {8, 6.1f, kScan16x4W4Q2}, {16, 9.6f, kScan16x4W4}, {32, 17.4f, kScan16x4W8}};
 
+// The static split of n >= 1 docs over a launch's `target` resident workgroups (or waves) and nq_groups query
+// groups: equal chunks, never more than docs, chunk_docs rounded up to a multiple of `round` (a power of 2).
+struct ChunkSplit { int64_t n_chunks, chunk_docs; };
+ChunkSplit chunk_split(int64_t n, int64_t target, int nq_groups, int64_t round = 1) {
+  int64_t n_chunks = target / nq_groups;   // never more workgroups than resident slots
+  if (n_chunks > n) n_chunks = n;
+  if (n_chunks < 1) n_chunks = 1;
+  const int64_t chunk_docs = ((n + n_chunks - 1) / n_chunks + round - 1) & ~(round - 1);
+  return {(n + chunk_docs - 1) / chunk_docs, chunk_docs};
+}
+
 template <int WAVES, int QW, int PER_CU, typename Kern>
 int launch_scan(Kern kern, cbv2_index* ix, const uint16_t* Q, int B, int lq, float* out, int64_t ld_out,
                 hipStream_t st, const char* name) {
   constexpr int QPB = WAVES * QW;
   const int nq_groups = (B + QPB - 1) / QPB;
   const int64_t target = (int64_t)PER_CU * cu_count(ix->device);  // resident workgroups
-  int64_t n_chunks = target / nq_groups;   // never more workgroups than resident slots
-  if (n_chunks < 1) n_chunks = 1;
-  if (n_chunks > ix->n) n_chunks = ix->n;
-  const int64_t chunk_docs = (ix->n + n_chunks - 1) / n_chunks;
-  n_chunks = (ix->n + chunk_docs - 1) / chunk_docs;
+  const auto [n_chunks, chunk_docs] = chunk_split(ix->n, target, nq_groups);
   const int64_t grid = (int64_t)nq_groups * n_chunks;
   if (grid > 0x7fffffff) return fail(CBV2_EUNSUPPORTED, "scan grid too large");
   hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(WAVES * 64), 0, st, ix->tokens, ix->doclens, ix->n, Q, B, lq,
@@ -6152,11 +6197,18 @@ bool stream_capturing(hipStream_t st) {
   return cs == hipStreamCaptureStatusActive;
 }
 
-int plan_split(cbv2_index* ix, int nq_groups, int64_t target, float dyn_frac, int task_docs, hipStream_t st,
-               ScanSplit* sp, int* ctr_ws) {
+// Static chunks per query group of a launch (plan_split's first step): the
+// slot count a fused top-k launch writes at most.
+int64_t scan_chunks(const cbv2_index* ix, int nq_groups, int64_t target) {
   int64_t n_chunks = target / nq_groups;   // never more workgroups than resident slots
   if (n_chunks < 1) n_chunks = 1;
   if (n_chunks > ix->n) n_chunks = ix->n;
+  return n_chunks;
+}
+
+int plan_split(cbv2_index* ix, int nq_groups, int64_t target, float dyn_frac, int task_docs, hipStream_t st,
+               ScanSplit* sp, int* ctr_ws) {
+  int64_t n_chunks = scan_chunks(ix, nq_groups, target);
   sp->task_docs = task_docs > 0 ? std::max(64, task_docs & ~63) : -std::max(4, (-task_docs) & ~3);
   sp->ctr = nullptr;
   sp->ring_slot = -1;
@@ -6218,39 +6270,39 @@ int finish_split(cbv2_index* ix, const ScanSplit& sp, hipStream_t st) {
   return CBV2_OK;
 }
 
-// Static chunks per query group of a launch (plan_split's first step): the
-// slot count a fused top-k launch writes at most.
-int64_t scan_chunks(const cbv2_index* ix, int nq_groups, int64_t target) {
-  int64_t n_chunks = target / nq_groups;   // never more workgroups than resident slots
-  if (n_chunks < 1) n_chunks = 1;
-  if (n_chunks > ix->n) n_chunks = ix->n;
-  return n_chunks;
-}
+// The bf16 doc-interleaved shapes (kBf16Shapes), each defined once: 4 waves x 1 / 2 / 4 queries, two workgroups per
+// CU, a 2-deep ring of 32-token iterations; 8 waves x 4 queries, one per CU, 64-token iterations, SPLITLOAD.
+constexpr Scan16x4Cfg kW4Q1{.waves = 4, .qw = 1, .nbuf = 2}, kW4Q2{.waves = 4, .qw = 2, .nbuf = 2},
+    kW4{.waves = 4, .qw = 4, .nbuf = 2}, kW8{.waves = 8, .qw = 4, .nbuf = 2, .tpi = 64, .splitload = true};
+// ... and what a dispatch site changes of one (Scan16x4Cfg and F8x4Cfg alike)
+template <typename Cfg> constexpr Cfg nt(Cfg c) { return c.aux = 2, c; }              // non-temporal doc stream
+template <typename Cfg> constexpr Cfg with_ld(Cfg c, int ld) { return c.ld = ld, c; }  // long documents
+template <typename Cfg> constexpr Cfg fused(Cfg c) { return c.fk = kFusedCap, c; }     // fused top-k
+constexpr Scan16x4Cfg with_bmk(Scan16x4Cfg c) { return c.bmk = true, c; }              // block keys folded in
+constexpr Scan16x4Cfg with_idx(Scan16x4Cfg c) { return c.idx = true, c; }              // subset scan
+// ONE workgroup per CU: a 3-deep ring, the lower half of the waves issue the LDS-DMA
+constexpr Scan16x4Cfg one_wg(Scan16x4Cfg c) { return c.nbuf = 3, c.occ = 1, c.splitload = true, c; }
 
-template <int WAVES, int QW, int PER_CU, int D, int NBUF, bool STAMPS, int TPI = 32, int OCC = 2, bool SPREAD = false,
-          int FK = 0, bool SPLITLOAD = false, bool ARRIVE = false, int PROBE = 0, int LD = kLd, int MORDER = 0,
-          int AUX = 0, bool BMK = false>
+template <Scan16x4Cfg C, int PER_CU>
 int launch_scan16x4(cbv2_index* ix, const uint16_t* Q, int B, int lq, float* out, int64_t ld_out, hipStream_t st,
                     float dyn_frac = kScanDynFrac, int task_docs = kScanTaskDocs, uint64_t* stamps = nullptr,
                     int* ctr_ws = nullptr, FusedTopk* ft = nullptr, uint32_t* bm = nullptr) {
-  constexpr int QPB = WAVES * QW;
+  constexpr int QPB = C.waves * C.qw;
   const int nq_groups = (B + QPB - 1) / QPB;
   ScanSplit sp;
   int rc = plan_split(ix, nq_groups, (int64_t)PER_CU * cu_count(ix->device), dyn_frac, task_docs, st, &sp, ctr_ws);
   if (rc != CBV2_OK) return rc;
-  if (FK > 0) {
-    if (ft == nullptr || ft->k < 1 || ft->k > FK - 16 || sp.n_chunks > ft->max_slots)
+  if (C.fk > 0) {
+    if (ft == nullptr || ft->k < 1 || ft->k > C.fk - 16 || sp.n_chunks > ft->max_slots)
       return fail(CBV2_EINVAL, "fused top-k: bad k or slot count");
     ft->slots = sp.n_chunks;
   }
-  if (BMK && bm == nullptr) return fail(CBV2_EINVAL, "block-key scan without keys");
-  hipLaunchKernelGGL((maxsim_scan16x4_kernel<WAVES, QW, D, NBUF, STAMPS, TPI, OCC, SPREAD, FK, SPLITLOAD, ARRIVE, PROBE, LD, MORDER,
-                                             AUX, BMK>),
-                     dim3((unsigned)(nq_groups * sp.n_chunks)), dim3(WAVES * 64), 0, st, ix->tokens, ix->doclens,
-                     ix->n, Q, B, lq, out, ld_out, sp.chunk_docs, sp.static_docs, sp.ctr, sp.task_docs,
-                     STAMPS ? stamps : g_clock_probe,
-                     ft ? ft->k : 0, ft ? ft->part : nullptr, ft ? (int)ft->max_slots : 0, sp.slices, bm,
-                     bm_blocks(ix->n), bm != nullptr ? bm_super_keys(bm, B, ix->n) : nullptr, bm_supers(ix->n));
+  if (C.bmk && bm == nullptr) return fail(CBV2_EINVAL, "block-key scan without keys");
+  hipLaunchKernelGGL(maxsim_scan16x4_kernel<C>, dim3((unsigned)(nq_groups * sp.n_chunks)), dim3(C.waves * 64), 0, st,
+                     ix->tokens, ix->doclens, ix->n, Q, B, lq, out, ld_out, sp.chunk_docs, sp.static_docs, sp.ctr,
+                     sp.task_docs, C.stamps ? stamps : g_clock_probe, ft ? ft->k : 0, ft ? ft->part : nullptr,
+                     ft ? (int)ft->max_slots : 0, sp.slices, bm, bm_blocks(ix->n),
+                     bm != nullptr ? bm_super_keys(bm, B, ix->n) : nullptr, bm_supers(ix->n));
   if ((rc = launch_check("maxsim_scan16x4_kernel"))) return rc;
   return finish_split(ix, sp, st);
 }
@@ -6267,11 +6319,7 @@ template <int QW>
 int launch_direct(cbv2_index* ix, const uint16_t* Q, int B, int lq, float* out, int64_t ld_out, hipStream_t st) {
   const int nq_groups = (B + QW - 1) / QW;
   const int64_t target_waves = 8LL * cu_count(ix->device) * kDirectOversub;  // 2 waves per SIMD, oversubscribed
-  int64_t n_chunks = target_waves / nq_groups;
-  if (n_chunks > ix->n) n_chunks = ix->n;
-  if (n_chunks < 1) n_chunks = 1;
-  const int64_t chunk_docs = (ix->n + n_chunks - 1) / n_chunks;
-  n_chunks = (ix->n + chunk_docs - 1) / chunk_docs;
+  const auto [n_chunks, chunk_docs] = chunk_split(ix->n, target_waves, nq_groups);
   const int64_t waves = (int64_t)nq_groups * n_chunks;
   const int64_t grid = (waves + 3) / 4;
   if (grid > 0x7fffffff) return fail(CBV2_EUNSUPPORTED, "scan grid too large");
@@ -6294,11 +6342,7 @@ int launch_pair(cbv2_index* ix, const uint16_t* Q, int B, int lq, float* out, in
   if (ix->dtype != CBV2_DTYPE_BF16) return fail(CBV2_EUNSUPPORTED, "pair scan: bf16 index only");
   const int nq_groups = (B + 2 * QW - 1) / (2 * QW);
   const int64_t target_wgs = 4LL * cu_count(ix->device) * kDirectOversub;
-  int64_t n_chunks = target_wgs / nq_groups;
-  if (n_chunks > ix->n) n_chunks = ix->n;
-  if (n_chunks < 1) n_chunks = 1;
-  const int64_t chunk_docs = (ix->n + n_chunks - 1) / n_chunks;
-  n_chunks = (ix->n + chunk_docs - 1) / chunk_docs;
+  const auto [n_chunks, chunk_docs] = chunk_split(ix->n, target_wgs, nq_groups);
   const int64_t grid = (int64_t)nq_groups * n_chunks;
   if (grid > 0x7fffffff) return fail(CBV2_EUNSUPPORTED, "scan grid too large");
   hipLaunchKernelGGL((maxsim_scan_pair_kernel<QW, 2>), dim3((unsigned)grid), dim3(128), 0, st, ix->tokens,
@@ -6306,29 +6350,27 @@ int launch_pair(cbv2_index* ix, const uint16_t* Q, int B, int lq, float* out, in
   return launch_check("maxsim_scan_pair_kernel");
 }
 
+constexpr StreamCfg kStreamQ1{.qw = 1, .aux = 2}, kStreamQ2{.qw = 2, .aux = 2};   // production B = 1 / 2: non-temporal
 // bm (nullable): fold the block and superblock maxima into the scan (chunks
 // rounded up to whole 256-doc superblocks; layout of bm_ws_bytes).
-template <int QW, int AUX, int WAVES = 4, int SLOTS = kStreamSlots, bool TW2 = false, bool PF = false>
+template <StreamCfg C>
 int launch_stream(cbv2_index* ix, const uint16_t* Q, int B, int lq, float* out, int64_t ld_out, hipStream_t st,
                   uint32_t* bm = nullptr) {
   if (ix->dtype != CBV2_DTYPE_BF16) return fail(CBV2_EUNSUPPORTED, "stream scan: bf16 index only");
-  const int nq_groups = (B + QW - 1) / QW;
-  const int64_t target_waves = (int64_t)WAVES * cu_count(ix->device) * kDirectOversub;
-  int64_t n_chunks = target_waves / nq_groups;
-  if (n_chunks > ix->n) n_chunks = ix->n;
-  if (n_chunks < 1) n_chunks = 1;
-  int64_t chunk_docs = (ix->n + n_chunks - 1) / n_chunks;
-  if (bm != nullptr) chunk_docs = (chunk_docs + 255) & ~(int64_t)255;   // whole superblocks
-  n_chunks = (ix->n + chunk_docs - 1) / chunk_docs;
-  const int64_t grid = ((int64_t)nq_groups * n_chunks + WAVES - 1) / WAVES;
+  const int nq_groups = (B + C.qw - 1) / C.qw;
+  const int64_t target_waves = (int64_t)C.waves * cu_count(ix->device) * kDirectOversub;
+  const auto [n_chunks, chunk_docs] = chunk_split(ix->n, target_waves, nq_groups, bm != nullptr ? 256 : 1);
+  const int64_t grid = ((int64_t)nq_groups * n_chunks + C.waves - 1) / C.waves;
   if (grid > 0x7fffffff) return fail(CBV2_EUNSUPPORTED, "scan grid too large");
-  hipLaunchKernelGGL((maxsim_scan_stream_kernel<QW, AUX, WAVES, SLOTS, TW2, PF>), dim3((unsigned)grid), dim3(WAVES * 64), 0, st,
-                     ix->tokens,
+  hipLaunchKernelGGL(maxsim_scan_stream_kernel<C>, dim3((unsigned)grid), dim3(C.waves * 64), 0, st, ix->tokens,
                      ix->doclens, ix->n, Q, B, lq, out, ld_out, chunk_docs, (int)ix->ld, bm, bm_blocks(ix->n),
                      bm ? bm_super_keys(bm, B, ix->n) : nullptr, bm_supers(ix->n));
   return launch_check("maxsim_scan_stream_kernel");
 }
 
+// A launch of scan_maxsim_long / scan_maxsim: the shape, its workgroups per CU, its dynamic share, the block keys.
+#define SCAN16X4(cfg, per_cu, dyn, bm) \
+  launch_scan16x4<cfg, per_cu>(ix, Q, B, lq, out, ld_out, st, dyn, kScanTaskDocs, nullptr, ctr_ws, nullptr, bm)
 // Long documents (index ld = 256 / 512 / 1024): B <= 8 the direct scan in
 // 128-token blocks, larger B the production 8-wave doc-interleaved scan with
 // its doc group spanning ld / 64 iterations (the row maxima carried across).
@@ -6338,18 +6380,13 @@ int scan_maxsim_long(cbv2_index* ix, const uint16_t* Q, int B, int lq, float* ou
   // sharing); B = 3-8 the direct scan, whose query groups share each doc's
   // tiles through L2
   if (B <= kDirectMaxB)
-    return B == 1 ? launch_stream<1, 2>(ix, Q, B, lq, out, ld_out, st) : launch_stream<2, 2>(ix, Q, B, lq, out, ld_out, st);
+    return B == 1 ? launch_stream<kStreamQ1>(ix, Q, B, lq, out, ld_out, st)
+                  : launch_stream<kStreamQ2>(ix, Q, B, lq, out, ld_out, st);
   if (B <= kLongDirectMaxB) return launch_direct<2>(ix, Q, B, lq, out, ld_out, st);
   switch (ix->ld) {
-    case 256:
-      return launch_scan16x4<8, 4, 1, 2, 2, false, 64, 2, false, 0, true, false, 0, 256>(
-          ix, Q, B, lq, out, ld_out, st, kScanDynFrac, kScanTaskDocs, nullptr, ctr_ws);
-    case 512:
-      return launch_scan16x4<8, 4, 1, 2, 2, false, 64, 2, false, 0, true, false, 0, 512>(
-          ix, Q, B, lq, out, ld_out, st, kScanDynFrac, kScanTaskDocs, nullptr, ctr_ws);
-    case 1024:
-      return launch_scan16x4<8, 4, 1, 2, 2, false, 64, 2, false, 0, true, false, 0, 1024>(
-          ix, Q, B, lq, out, ld_out, st, kScanDynFrac, kScanTaskDocs, nullptr, ctr_ws);
+    case 256: return SCAN16X4(with_ld(kW8, 256), 1, kScanDynFrac, nullptr);
+    case 512: return SCAN16X4(with_ld(kW8, 512), 1, kScanDynFrac, nullptr);
+    case 1024: return SCAN16X4(with_ld(kW8, 1024), 1, kScanDynFrac, nullptr);
     default:
       return fail(CBV2_EUNSUPPORTED, "index ld %d not built", (int)ix->ld);
   }
@@ -6376,15 +6413,14 @@ int scan_maxsim(cbv2_index* ix, const uint16_t* Q, int B, int lq, float* out, in
     return scan_maxsim_long(ix, Q, B, lq, out, ld_out, st, ctr_ws);
   }
   if (ft != nullptr)   // fused top-k: the B > 16 doc-interleaved scan only (fused_eligible)
-    return launch_scan16x4<8, 4, 1, 2, 2, false, 64, 2, false, kFusedCap, true>(ix, Q, B, lq, nullptr, 0, st,
-                                                                               kScanDynFrac, kScanTaskDocs, nullptr,
-                                                                               ctr_ws, ft);
+    return launch_scan16x4<fused(kW8), 1>(ix, Q, B, lq, nullptr, 0, st, kScanDynFrac, kScanTaskDocs, nullptr, ctr_ws,
+                                          ft);
   if (variant == kScanAuto) {
     // dense docs: B <= 2 takes the 4 x 1 shape below (bm == nullptr: its
     // caller runs the block maxima, scan_folds_bmax)
     if (B <= kDirectMaxB && !ix->dense_docs)
-      return B == 1 ? launch_stream<1, 2>(ix, Q, B, lq, out, ld_out, st, bm)
-                    : launch_stream<2, 2>(ix, Q, B, lq, out, ld_out, st, bm);
+      return B == 1 ? launch_stream<kStreamQ1>(ix, Q, B, lq, out, ld_out, st, bm)
+                    : launch_stream<kStreamQ2>(ix, Q, B, lq, out, ld_out, st, bm);
     variant = pick_shape(kBf16Shapes, B);
   }
   switch (variant) {
@@ -6396,88 +6432,58 @@ int scan_maxsim(cbv2_index* ix, const uint16_t* Q, int B, int lq, float* out, in
       // 6.88 TB/s), 100k 0.517 -> 0.494 (3-deep, no SPLITLOAD), 1M 4.594 ->
       // 4.522; at B = 4 (every slot live) the two-per-CU form stays (4.70 vs
       // 5.54 ms: one wave per SIMD cannot hide the MFMA latency)
-      if (B <= kOneWgMaxB && bm != nullptr)
-        return launch_scan16x4<4, 1, 1, 2, 3, false, 32, 1, false, 0, true, false, 0, kLd, 0, 2, true>(
-            ix, Q, B, lq, out, ld_out, st, kScanDynFracOneWg, kScanTaskDocs, nullptr, ctr_ws, nullptr, bm);
-      if (B <= kOneWgMaxB)
-        return launch_scan16x4<4, 1, 1, 2, 3, false, 32, 1, false, 0, true, false, 0, kLd, 0, 2>(
-            ix, Q, B, lq, out, ld_out, st, kScanDynFracOneWg, kScanTaskDocs, nullptr, ctr_ws);
+      if (B <= kOneWgMaxB && bm != nullptr) return SCAN16X4(with_bmk(nt(one_wg(kW4Q1))), 1, kScanDynFracOneWg, bm);
+      if (B <= kOneWgMaxB) return SCAN16X4(nt(one_wg(kW4Q1)), 1, kScanDynFracOneWg, nullptr);
       if (B <= 4 && bm != nullptr)   // the block keys folded in (zeroed by the caller: scan_folds_bmax_zeroed)
-        return launch_scan16x4<4, 1, 2, 2, 2, false, 32, 2, false, 0, false, false, 0, kLd, 0, 2, true>(
-            ix, Q, B, lq, out, ld_out, st, kScanDynFracSmallB, kScanTaskDocs, nullptr, ctr_ws, nullptr, bm);
+        return SCAN16X4(with_bmk(nt(kW4Q1)), 2, kScanDynFracSmallB, bm);
       if (B <= 4)           // one query group: every doc byte is read once (non-temporal)
-        return launch_scan16x4<4, 1, 2, 2, 2, false, 32, 2, false, 0, false, false, 0, kLd, 0, 2>(
-            ix, Q, B, lq, out, ld_out, st, kScanDynFracSmallB, kScanTaskDocs, nullptr, ctr_ws);
-      return launch_scan16x4<4, 1, 2, 2, 2, false>(ix, Q, B, lq, out, ld_out, st, kScanDynFracSmallB, kScanTaskDocs,
-                                                   nullptr, ctr_ws);
+        return SCAN16X4(nt(kW4Q1), 2, kScanDynFracSmallB, nullptr);
+      return SCAN16X4(kW4Q1, 2, kScanDynFracSmallB, nullptr);
     case kScan16x4W8:   // SPLITLOAD: lab, same box, 1M / 125k / B=64: 145.25 -> 144.10, 18.14 -> 17.97, 37.98 -> 37.53 ms
-      return launch_scan16x4<8, 4, 1, 2, 2, false, 64, 2, false, 0, true>(ix, Q, B, lq, out, ld_out, st, kScanDynFrac,
-                                                                          kScanTaskDocs, nullptr, ctr_ws);
+      return SCAN16X4(kW8, 1, kScanDynFrac, nullptr);
     case kScan16x4W4:
-      if (B <= 16)          // one query group: non-temporal doc stream
-        return launch_scan16x4<4, 4, 2, 2, 2, false, 32, 2, false, 0, false, false, 0, kLd, 0, 2>(
-            ix, Q, B, lq, out, ld_out, st, kScanDynFracB16, kScanTaskDocs, nullptr, ctr_ws);
-      return launch_scan16x4<4, 4, 2, 2, 2, false>(ix, Q, B, lq, out, ld_out, st, kScanDynFracB16, kScanTaskDocs,
-                                                   nullptr, ctr_ws);
+      if (B <= 16) return SCAN16X4(nt(kW4), 2, kScanDynFracB16, nullptr);   // one query group: non-temporal doc stream
+      return SCAN16X4(kW4, 2, kScanDynFracB16, nullptr);
     case kScan16x4W4Q2:   // 8 queries per workgroup (2 per wave)
-      if (B <= 8)         // one query group: non-temporal doc stream
-        return launch_scan16x4<4, 2, 2, 2, 2, false, 32, 2, false, 0, false, false, 0, kLd, 0, 2>(
-            ix, Q, B, lq, out, ld_out, st, kScanDynFracSmallB, kScanTaskDocs, nullptr, ctr_ws);
-      return launch_scan16x4<4, 2, 2, 2, 2, false>(ix, Q, B, lq, out, ld_out, st, kScanDynFracSmallB, kScanTaskDocs,
-                                                   nullptr, ctr_ws);
+      if (B <= 8) return SCAN16X4(nt(kW4Q2), 2, kScanDynFracSmallB, nullptr);   // one query group: non-temporal doc stream
+      return SCAN16X4(kW4Q2, 2, kScanDynFracSmallB, nullptr);
 #ifdef CBV2_LAB   // variants tools/scan_lab.hip A/Bs (the product never dispatches them: its library leaves them out)
-    case kScanDirectQ1:
-      return launch_direct<1>(ix, Q, B, lq, out, ld_out, st);
-    case kScanDirectQ2:
-      return launch_direct<2>(ix, Q, B, lq, out, ld_out, st);
-    case kScanStreamQ1:
-      return launch_stream<1, 2>(ix, Q, B, lq, out, ld_out, st);
-    case kScanStreamQ2:
-      return launch_stream<2, 2>(ix, Q, B, lq, out, ld_out, st);
-    case kScanStreamQ1Cached:
-      return launch_stream<1, 0>(ix, Q, B, lq, out, ld_out, st);
+    case kScanDirectQ1: return launch_direct<1>(ix, Q, B, lq, out, ld_out, st);
+    case kScanDirectQ2: return launch_direct<2>(ix, Q, B, lq, out, ld_out, st);
+    case kScanStreamQ1: return launch_stream<kStreamQ1>(ix, Q, B, lq, out, ld_out, st);
+    case kScanStreamQ2: return launch_stream<kStreamQ2>(ix, Q, B, lq, out, ld_out, st);
+    case kScanStreamQ1Cached: return launch_stream<StreamCfg{.qw = 1, .aux = 0}>(ix, Q, B, lq, out, ld_out, st);
     case kScanStreamQ1W8:   // lab: 8 waves x 4 tile slots per CU
-      return launch_stream<1, 2, 8, 4>(ix, Q, B, lq, out, ld_out, st);
+      return launch_stream<StreamCfg{.qw = 1, .aux = 2, .waves = 8, .slots = 4}>(ix, Q, B, lq, out, ld_out, st);
     // lab, 1M docs, same process (profiles/r03z_lab_stream_qg_1m.log): B=4
     // 5.72 ms vs 5.69 for variant 13; B=8 9.95 (18) / 8.58 (19) vs 5.98: not kept
-    case kScanStreamQ4:     // lab: B <= 4 in one query group
-      return launch_stream<4, 2>(ix, Q, B, lq, out, ld_out, st);
-    case kScanStreamQ8:     // lab: B <= 8 in one query group
-      return launch_stream<8, 2>(ix, Q, B, lq, out, ld_out, st);
-    case kScanStreamQ1Tw2:  // lab: two tiles per wait
-      return launch_stream<1, 2, 4, kStreamSlots, true>(ix, Q, B, lq, out, ld_out, st);
-    case kScanStreamQ2Tw2:
-      return launch_stream<2, 2, 4, kStreamSlots, true>(ix, Q, B, lq, out, ld_out, st);
-    case kScanPairQ1:       // lab: two waves sharing one tile ring, 1 / 2 / 4 queries each
-      return launch_pair<1>(ix, Q, B, lq, out, ld_out, st);
-    case kScanPairQ2:
-      return launch_pair<2>(ix, Q, B, lq, out, ld_out, st);
-    case kScanPairQ4:
-      return launch_pair<4>(ix, Q, B, lq, out, ld_out, st);
+    // lab: B <= 4 in one query group
+    case kScanStreamQ4: return launch_stream<StreamCfg{.qw = 4, .aux = 2}>(ix, Q, B, lq, out, ld_out, st);
+    // lab: B <= 8 in one query group
+    case kScanStreamQ8: return launch_stream<StreamCfg{.qw = 8, .aux = 2}>(ix, Q, B, lq, out, ld_out, st);
+    // lab: two tiles per wait
+    case kScanStreamQ1Tw2: return launch_stream<StreamCfg{.qw = 1, .aux = 2, .tw2 = true}>(ix, Q, B, lq, out, ld_out, st);
+    case kScanStreamQ2Tw2: return launch_stream<StreamCfg{.qw = 2, .aux = 2, .tw2 = true}>(ix, Q, B, lq, out, ld_out, st);
+    // lab: two waves sharing one tile ring, 1 / 2 / 4 queries each
+    case kScanPairQ1: return launch_pair<1>(ix, Q, B, lq, out, ld_out, st);
+    case kScanPairQ2: return launch_pair<2>(ix, Q, B, lq, out, ld_out, st);
+    case kScanPairQ4: return launch_pair<4>(ix, Q, B, lq, out, ld_out, st);
     // lab, round 4, 1M docs, same process (profiles/r04l_lab_midbatch.log): the
     // prefetching stream 5.78 vs 5.82 ms at B=4, 4.76 vs 4.78 at B=1 -- not
     // kept; 8 waves x 1 query (30 / 31) 7.1-7.6 ms at B=5-8 vs 4 x 2's 6.1-6.4
-    case kScanStreamQ4Pf:   // lab: the next tile's fragments read under this tile's MFMAs
-      return launch_stream<4, 2, 4, kStreamSlots, false, true>(ix, Q, B, lq, out, ld_out, st);
-    case kScanStreamQ1Pf:
-      return launch_stream<1, 2, 4, kStreamSlots, false, true>(ix, Q, B, lq, out, ld_out, st);
-    case kScanStreamQ2Pf:
-      return launch_stream<2, 2, 4, kStreamSlots, false, true>(ix, Q, B, lq, out, ld_out, st);
-    case kScan16x4W4Q1Nt:   // lab: 4 x 1 / 4 x 2 with the non-temporal doc stream (one query group per launch)
-      return launch_scan16x4<4, 1, 2, 2, 2, false, 32, 2, false, 0, false, false, 0, kLd, 0, 2>(
-          ix, Q, B, lq, out, ld_out, st, kScanDynFracSmallB, kScanTaskDocs, nullptr, ctr_ws);
-    case kScan16x4W4Q2Nt:
-      return launch_scan16x4<4, 2, 2, 2, 2, false, 32, 2, false, 0, false, false, 0, kLd, 0, 2>(
-          ix, Q, B, lq, out, ld_out, st, kScanDynFracSmallB, kScanTaskDocs, nullptr, ctr_ws);
-    case kScan16x4W4Nt:     // lab: 4 x 4 with the non-temporal doc stream (B <= 16: one query group)
-      return launch_scan16x4<4, 4, 2, 2, 2, false, 32, 2, false, 0, false, false, 0, kLd, 0, 2>(
-          ix, Q, B, lq, out, ld_out, st, kScanDynFracB16, kScanTaskDocs, nullptr, ctr_ws);
-    case kScan16x4W8Q1:     // lab: 8 queries per workgroup, one per wave (2 waves per SIMD)
-      return launch_scan16x4<8, 1, 1, 2, 2, false>(ix, Q, B, lq, out, ld_out, st, kScanDynFracSmallB, kScanTaskDocs,
-                                                   nullptr, ctr_ws);
-    case kScan16x4W8Q1x2:   // lab: the same, two workgroups per CU
-      return launch_scan16x4<8, 1, 2, 2, 2, false, 32, 4>(ix, Q, B, lq, out, ld_out, st, kScanDynFracSmallB,
-                                                          kScanTaskDocs, nullptr, ctr_ws);
+    // lab: the next tile's fragments read under this tile's MFMAs
+    case kScanStreamQ4Pf: return launch_stream<StreamCfg{.qw = 4, .aux = 2, .pf = true}>(ix, Q, B, lq, out, ld_out, st);
+    case kScanStreamQ1Pf: return launch_stream<StreamCfg{.qw = 1, .aux = 2, .pf = true}>(ix, Q, B, lq, out, ld_out, st);
+    case kScanStreamQ2Pf: return launch_stream<StreamCfg{.qw = 2, .aux = 2, .pf = true}>(ix, Q, B, lq, out, ld_out, st);
+    // lab: 4 x 1 / 4 x 2 with the non-temporal doc stream (one query group per launch)
+    case kScan16x4W4Q1Nt: return SCAN16X4(nt(kW4Q1), 2, kScanDynFracSmallB, nullptr);
+    case kScan16x4W4Q2Nt: return SCAN16X4(nt(kW4Q2), 2, kScanDynFracSmallB, nullptr);
+    // lab: 4 x 4 with the non-temporal doc stream (B <= 16: one query group)
+    case kScan16x4W4Nt: return SCAN16X4(nt(kW4), 2, kScanDynFracB16, nullptr);
+    // lab: 8 queries per workgroup, one per wave (2 waves per SIMD)
+    case kScan16x4W8Q1: return SCAN16X4((Scan16x4Cfg{.waves = 8, .qw = 1, .nbuf = 2}), 1, kScanDynFracSmallB, nullptr);
+    // lab: the same, two workgroups per CU
+    case kScan16x4W8Q1x2: return SCAN16X4((Scan16x4Cfg{.waves = 8, .qw = 1, .nbuf = 2, .occ = 4}), 2, kScanDynFracSmallB, nullptr);
     case kScan32Shfl:
       return launch_scan<4, 4, 2>(maxsim_scan_kernel<4, 4, false>, ix, Q, B, lq, out, ld_out, st, "maxsim_scan_kernel");
     case kScan32Dpp:
@@ -6500,6 +6506,7 @@ int scan_maxsim(cbv2_index* ix, const uint16_t* Q, int B, int lq, float* out, in
     default:
       return fail(CBV2_EINVAL, "unknown scan variant %d", variant);
   }
+#undef SCAN16X4
 }
 
 // B <= 2: the direct scan (HBM-bound); 3 <= B <= 8: the doc-interleaved scan
@@ -6508,6 +6515,15 @@ int scan_maxsim(cbv2_index* ix, const uint16_t* Q, int B, int lq, float* out, in
 // 8 waves x 8 queries.
 constexpr int kF8DirectMaxB = 2;
 constexpr int kF8SmallMaxB = 8;
+// scan_f8's shape ids (tools/scan_lab.py passes the numbers: they stay); 5, 7, 8, 9, 24: production, the rest lab.
+enum F8Shape {
+  kF8ShapeAuto = 0, kF8ShapeW8Q8NoPf = 1, kF8ShapeTpi64N2 = 2, kF8ShapeTpi64N3 = 3, kF8ShapeTpi128N2 = 4,
+  kF8ShapeW8Q8 = 5, kF8ShapeTpi64N2Pf = 6, kF8ShapeW4Q4 = 7, kF8ShapeW4Q8 = 8, kF8ShapeW4Q2 = 9, kF8ShapeW4Q2x3 = 10,
+  kF8ShapeW8Q8Round2 = 11, kF8ShapeW8Q8Ring3 = 12, kF8ShapeSpread2 = 13, kF8ShapeSplit = 14, kF8ShapeSpread2Split = 15,
+  kF8ShapeQuad = 16, kF8ShapeProbeNoFold = 17, kF8ShapeProbeNoSums = 18, kF8ShapeStreamW4S16Tw1 = 19,
+  kF8ShapeDirect = 20, kF8ShapeStreamW16S4Tw1 = 21, kF8ShapeStreamW8S8Tw1 = 22, kF8ShapeStreamW4S16 = 23,
+  kF8ShapeW4Q1 = 24, kF8ShapeStream = 25
+};
 // MXFP8 shapes (scan_f8's shape ids), ms per query group at 1M docs: 9 = 4
 // waves x 2 queries, two per CU (3.0; B=8 alone 3.74); 7 = 4 x 4, three per
 // CU (5.2; B=16 alone 5.81); 8 = 4 x 8, two per CU (9.5); 5 = 8 x 8, one per
@@ -6518,7 +6534,8 @@ constexpr int kF8SmallMaxB = 8;
 // B=4, 2.79 -> 2.38 at B=3, 1M docs; the one-group launches of 9 and 7 stream
 // non-temporally and skip padded slots: B=5 3.50 -> 3.40, B=12 5.30 -> 5.08;
 // profiles/r04aa_lab_f8_midbatch.log)
-constexpr ShapeCost kF8Shapes[] = {{4, 2.45f, 24}, {8, 3.0f, 9}, {16, 5.2f, 7}, {32, 9.5f, 8}, {64, 18.2f, 5}};
+constexpr ShapeCost kF8Shapes[] = {{4, 2.45f, kF8ShapeW4Q1}, {8, 3.0f, kF8ShapeW4Q2}, {16, 5.2f, kF8ShapeW4Q4},
+                                   {32, 9.5f, kF8ShapeW4Q8}, {64, 18.2f, kF8ShapeW8Q8}};
 constexpr int kF8Waves = 8, kF8QW = 8;
 // Fold distance of the doc-interleaved f8 scans: a chain's row max is folded
 // 3 MFMAs after it issues (no MFMA -> VALU hazard pads: 122 -> 36 s_nop per
@@ -6542,29 +6559,36 @@ constexpr float kF8DynAuto = -1.0f;
 constexpr float kF8DynSmall = 0.6f;   // shapes 7 and 8
 constexpr float kF8DynB8 = 0.3f;      // shape 9
 
+// The MXFP8 doc-interleaved shapes (kF8Shapes), each defined once (32-token iterations, a 3-deep ring): 8 waves x 8
+// queries, one workgroup per CU; 4 x 4, three per CU; 4 x 8, 4 x 2 and 4 x 1, two per CU.  nt / with_ld / fused as above.
+constexpr F8x4Cfg kF8W8Q8Ring3{.waves = kF8Waves, .qw = kF8QW, .d = kF8D, .pf = true, .pqs = true},
+    kF8W4Q4{.waves = 4, .qw = 4, .d = kF8D47, .pf = true, .occ = 3, .pqs = true},
+    kF8W4Q8{.waves = 4, .qw = 8, .d = kF8D47, .pf = true, .pqs = true},
+    kF8W4Q2{.waves = 4, .qw = 2, .d = kF8D, .pf = true, .pqs = true},
+    kF8W4Q1{.waves = 4, .qw = 1, .pf = true, .pqs = true};
+// PAIR: n = 2 iterations per barrier on 4 ring slots (QUAD, lab: 4 on 8)
+constexpr F8x4Cfg paired(F8x4Cfg c, int n = 2) { return c.nbuf = 2 * n, c.pair = true, c.quad = n == 4, c; }
+constexpr F8x4Cfg kF8W8Q8 = paired(kF8W8Q8Ring3);
+
 // QW queries per wave, PER_CU workgroups per CU in the split, OCC the
 // launch-bounds occupancy hint (production: 8 waves x 8 queries, one per CU).
-template <int TPI, int NBUF, bool PF = false, int QW = kF8QW, int PER_CU = 1, int OCC = 2, int WAVES = kF8Waves,
-          int FK = 0, int LD = kLd, int D = 1, bool PQS = false, bool PAIR = false, bool SPREAD2 = false,
-          bool SPLIT = false, bool QUAD = false, int PROBE = 0, int AUX = 0>
+template <F8x4Cfg C, int PER_CU>
 int launch_f8x4(cbv2_index* ix, const uint8_t* Qb, const uint8_t* Qs, int B, int lq, float* out, int64_t ld_out,
                 hipStream_t st, float dyn_frac, int task_docs, int* ctr_ws = nullptr, FusedTopk* ft = nullptr) {
-  constexpr int QPB = WAVES * QW;
+  constexpr int QPB = C.waves * C.qw;
   const int nq_groups = (B + QPB - 1) / QPB;
   ScanSplit sp;
   int rc = plan_split(ix, nq_groups, (int64_t)PER_CU * cu_count(ix->device), dyn_frac, task_docs, st, &sp, ctr_ws);
   if (rc != CBV2_OK) return rc;
-  if (FK > 0) {
-    if (ft == nullptr || ft->k < 1 || ft->k > FK - 16 || sp.n_chunks > ft->max_slots)
+  if (C.fk > 0) {
+    if (ft == nullptr || ft->k < 1 || ft->k > C.fk - 16 || sp.n_chunks > ft->max_slots)
       return fail(CBV2_EINVAL, "fused top-k: bad k or slot count");
     ft->slots = sp.n_chunks;
   }
-  hipLaunchKernelGGL((maxsim_scan_f8x4_kernel<WAVES, QW, D, NBUF, TPI, PF, OCC, FK, LD, PQS, PAIR, SPREAD2, SPLIT, QUAD, PROBE,
-                                              AUX>),
-                     dim3((unsigned)(nq_groups * sp.n_chunks)), dim3(WAVES * 64), 0, st, ix->tokens, ix->scales,
-                     ix->doclens, ix->n, Qb, Qs, B, lq, out, ld_out, sp.chunk_docs, sp.static_docs, sp.ctr,
-                     sp.task_docs, ft ? ft->k : 0, ft ? ft->part : nullptr, ft ? (int)ft->max_slots : 0, sp.slices,
-                     g_clock_probe);
+  hipLaunchKernelGGL(maxsim_scan_f8x4_kernel<C>, dim3((unsigned)(nq_groups * sp.n_chunks)), dim3(C.waves * 64), 0, st,
+                     ix->tokens, ix->scales, ix->doclens, ix->n, Qb, Qs, B, lq, out, ld_out, sp.chunk_docs,
+                     sp.static_docs, sp.ctr, sp.task_docs, ft ? ft->k : 0, ft ? ft->part : nullptr,
+                     ft ? (int)ft->max_slots : 0, sp.slices, g_clock_probe);
   if ((rc = launch_check("maxsim_scan_f8x4_kernel"))) return rc;
   return finish_split(ix, sp, st);
 }
@@ -6577,28 +6601,23 @@ template <int LD>
 int launch_f8_long(cbv2_index* ix, const uint8_t* Qb, const uint8_t* Qs, int B, int lq, float* out, int64_t ld_out,
                    hipStream_t st, int* ctr_ws) {
   if (B <= kF8SmallMaxB)
-    return launch_f8x4<32, 3, true, 2, 2, 2, 4, 0, LD, kF8D, true>(ix, Qb, Qs, B, lq, out, ld_out, st, kF8DynB8,
-                                                                   kScanTaskDocs, ctr_ws);
-  return launch_f8x4<32, 3, true, kF8QW, 1, 2, kF8Waves, 0, LD, kF8D, true>(ix, Qb, Qs, B, lq, out, ld_out, st,
-                                                                            kScanDynFrac, kScanTaskDocs, ctr_ws);
+    return launch_f8x4<with_ld(kF8W4Q2, LD), 2>(ix, Qb, Qs, B, lq, out, ld_out, st, kF8DynB8, kScanTaskDocs, ctr_ws);
+  return launch_f8x4<with_ld(kF8W8Q8Ring3, LD), 1>(ix, Qb, Qs, B, lq, out, ld_out, st, kScanDynFrac, kScanTaskDocs,
+                                                   ctr_ws);
 }
 
 // The MXFP8 streaming scan (B <= 2, any ld): one 4-wave workgroup per CU,
 // chunks for kDirectOversub x the resident waves.
-template <int WAVES = 8, int SLOTS = 8, bool TW2 = true>
+constexpr F8StreamCfg kF8Stream{.qw = 2, .aux = 2, .waves = 8, .slots = 8};   // production (TW2)
+template <F8StreamCfg C = kF8Stream>
 int launch_f8_stream(cbv2_index* ix, const uint8_t* Qb, const uint8_t* Qs, int B, int lq, float* out, int64_t ld_out,
                      hipStream_t st) {
-  constexpr int QW = 2;
-  const int nq_groups = (B + QW - 1) / QW;
-  int64_t n_chunks = (int64_t)WAVES * cu_count(ix->device) * kDirectOversub / nq_groups;
-  if (n_chunks > ix->n) n_chunks = ix->n;
-  if (n_chunks < 1) n_chunks = 1;
-  const int64_t chunk_docs = (ix->n + n_chunks - 1) / n_chunks;
-  n_chunks = (ix->n + chunk_docs - 1) / chunk_docs;
-  const int64_t grid = ((int64_t)nq_groups * n_chunks + WAVES - 1) / WAVES;
+  const int nq_groups = (B + C.qw - 1) / C.qw;
+  const auto [n_chunks, chunk_docs] =
+      chunk_split(ix->n, (int64_t)C.waves * cu_count(ix->device) * kDirectOversub, nq_groups);
+  const int64_t grid = ((int64_t)nq_groups * n_chunks + C.waves - 1) / C.waves;
   if (grid > 0x7fffffff) return fail(CBV2_EUNSUPPORTED, "scan grid too large");
-  hipLaunchKernelGGL((maxsim_scan_f8_stream_kernel<QW, 2, WAVES, SLOTS, TW2>), dim3((unsigned)grid), dim3(WAVES * 64), 0, st,
-                     ix->tokens,
+  hipLaunchKernelGGL(maxsim_scan_f8_stream_kernel<C>, dim3((unsigned)grid), dim3(C.waves * 64), 0, st, ix->tokens,
                      ix->scales, ix->doclens, ix->n, Qb, Qs, B, lq, out, ld_out, chunk_docs, (int)ix->ld);
   return launch_check("maxsim_scan_f8_stream_kernel");
 }
@@ -6616,42 +6635,41 @@ int scan_f8_long(cbv2_index* ix, const uint8_t* Qb, const uint8_t* Qs, int B, in
 }
 
 int scan_f8(cbv2_index* ix, const uint8_t* Qb, int B, int lq, float* out, int64_t ld_out, hipStream_t st,
-            float dyn_frac = kF8DynAuto, int task_docs = kScanTaskDocs, int shape = 0, int* ctr_ws = nullptr,
-            FusedTopk* ft = nullptr) {
+            float dyn_frac = kF8DynAuto, int task_docs = kScanTaskDocs, int shape = kF8ShapeAuto,
+            int* ctr_ws = nullptr, FusedTopk* ft = nullptr) {
   if (ix->n == 0) return CBV2_OK;
   const uint8_t* Qs = Qb + (size_t)B * lq * kDim;
   const bool auto_frac = dyn_frac < 0.0f;
   auto frac = [&](float d) { return auto_frac ? d : dyn_frac; };
   if (ix->ld != kLd) {   // long documents: automatic shape only (B <= 8 direct, else 8 waves x 8 queries)
-    if (ft != nullptr || shape != 0) return fail(CBV2_EUNSUPPORTED, "long-doc index: automatic scan only");
+    if (ft != nullptr || shape != kF8ShapeAuto) return fail(CBV2_EUNSUPPORTED, "long-doc index: automatic scan only");
     return scan_f8_long(ix, Qb, Qs, B, lq, out, ld_out, st, ctr_ws);
   }
 #ifdef CBV2_LAB   // fused top-k on MXFP8 (A/B only: its build spills; fused_slots never picks it in the product)
   if (ft != nullptr)
-    return launch_f8x4<32, 3, true, kF8QW, 1, 2, kF8Waves, kFusedCap>(ix, Qb, Qs, B, lq, nullptr, 0, st,
-                                                                      frac(kScanDynFrac), task_docs, ctr_ws, ft);
+    return launch_f8x4<fused(F8x4Cfg{.waves = kF8Waves, .qw = kF8QW, .pf = true}), 1>(
+        ix, Qb, Qs, B, lq, nullptr, 0, st, frac(kScanDynFrac), task_docs, ctr_ws, ft);
 #else
   if (ft != nullptr) return fail(CBV2_EUNSUPPORTED, "fused top-k: not built for MXFP8 indexes");
 #endif
   // dense docs (CBV2_OPT_DENSE_DOCS): B <= 2 too on the 4 x 1 shape (every slot streamed)
-  if ((B > kF8DirectMaxB || ix->dense_docs) && shape == 0) shape = pick_shape(kF8Shapes, B);
-  if (B <= kF8DirectMaxB && shape == 0) return launch_f8_stream(ix, Qb, Qs, B, lq, out, ld_out, st);
+  if ((B > kF8DirectMaxB || ix->dense_docs) && shape == kF8ShapeAuto) shape = pick_shape(kF8Shapes, B);
+  if (B <= kF8DirectMaxB && shape == kF8ShapeAuto) return launch_f8_stream(ix, Qb, Qs, B, lq, out, ld_out, st);
 #ifdef CBV2_LAB   // shapes tools/scan_lab.hip A/Bs (the product's library leaves them out)
-  if (B <= kF8DirectMaxB && shape == 25) return launch_f8_stream(ix, Qb, Qs, B, lq, out, ld_out, st);  // lab
-  if (B <= kF8DirectMaxB && shape == 19) return launch_f8_stream<4, 16, false>(ix, Qb, Qs, B, lq, out, ld_out, st);  // lab
-  if (B <= kF8DirectMaxB && shape == 21) return launch_f8_stream<16, 4, false>(ix, Qb, Qs, B, lq, out, ld_out, st);  // lab
-  // lab: one tile per wait (the production 8 x 8 ring before TW2) / TW2 at 4 x 16
-  if (B <= kF8DirectMaxB && shape == 22) return launch_f8_stream<8, 8, false>(ix, Qb, Qs, B, lq, out, ld_out, st);
-  if (B <= kF8DirectMaxB && shape == 23) return launch_f8_stream<4, 16, true>(ix, Qb, Qs, B, lq, out, ld_out, st);
-  if (B <= kF8DirectMaxB && shape == 20) {   // lab: the direct scan
+  if (B <= kF8DirectMaxB) {
+    // lab: one tile per wait (the production 8 x 8 ring before TW2) / TW2 at 4 x 16
+    constexpr F8StreamCfg w4{.qw = 2, .aux = 2, .waves = 4, .slots = 16}, w16{.qw = 2, .aux = 2, .waves = 16, .slots = 4};
+    constexpr auto tw1 = [](F8StreamCfg c) { return c.tw2 = false, c; };
+    if (shape == kF8ShapeStream) return launch_f8_stream(ix, Qb, Qs, B, lq, out, ld_out, st);
+    if (shape == kF8ShapeStreamW4S16Tw1) return launch_f8_stream<tw1(w4)>(ix, Qb, Qs, B, lq, out, ld_out, st);
+    if (shape == kF8ShapeStreamW16S4Tw1) return launch_f8_stream<tw1(w16)>(ix, Qb, Qs, B, lq, out, ld_out, st);
+    if (shape == kF8ShapeStreamW8S8Tw1) return launch_f8_stream<tw1(kF8Stream)>(ix, Qb, Qs, B, lq, out, ld_out, st);
+    if (shape == kF8ShapeStreamW4S16) return launch_f8_stream<w4>(ix, Qb, Qs, B, lq, out, ld_out, st);
+  }
+  if (B <= kF8DirectMaxB && shape == kF8ShapeDirect) {   // lab: the direct scan
     constexpr int QW = 2;
     const int nq_groups = (B + QW - 1) / QW;
-    const int64_t target_waves = 8LL * cu_count(ix->device);
-    int64_t n_chunks = target_waves / nq_groups;
-    if (n_chunks > ix->n) n_chunks = ix->n;
-    if (n_chunks < 1) n_chunks = 1;
-    const int64_t chunk_docs = (ix->n + n_chunks - 1) / n_chunks;
-    n_chunks = (ix->n + chunk_docs - 1) / chunk_docs;
+    const auto [n_chunks, chunk_docs] = chunk_split(ix->n, 8LL * cu_count(ix->device), nq_groups);
     const int64_t grid = ((int64_t)nq_groups * n_chunks + 3) / 4;
     hipLaunchKernelGGL(maxsim_scan_f8_direct_kernel<QW>, dim3((unsigned)grid), dim3(256), 0, st, ix->tokens,
                        ix->scales, ix->doclens, ix->n, Qb, Qs, B, lq, out, ld_out, chunk_docs, kLd);
@@ -6666,62 +6684,54 @@ int scan_f8(cbv2_index* ix, const uint8_t* Qb, int B, int lq, float* out, int64_
   // A/B only: 1 = 5 without PF, 2 = 64 / 2-deep, 3 = 64 / 3-deep, 4 = 128 /
   // 2-deep (2-4 spill at 8 queries per wave), 6 = 2 with PF, 10 = 9 with
   // three workgroups per CU.
+#ifdef CBV2_LAB   // what the lab shapes change of a production one
+  constexpr F8x4Cfg kW8Q8Plain{.waves = kF8Waves, .qw = kF8QW};   // lab: no PF, fold distance 1, unpacked scales
+  constexpr auto ring = [](F8x4Cfg c, int tpi, int nbuf) { return c.tpi = tpi, c.nbuf = nbuf, c; };
+  constexpr auto pf = [](F8x4Cfg c) { return c.pf = true, c; };
+  constexpr auto spread2 = [](F8x4Cfg c) { return c.spread2 = true, c; };
+  constexpr auto split = [](F8x4Cfg c) { return c.split = true, c; };
+  constexpr auto probe = [](F8x4Cfg c, int p) { return c.probe = p, c; };
+#endif
+#define F8X4(cfg, per_cu, dyn) launch_f8x4<cfg, per_cu>(ix, Qb, Qs, B, lq, out, ld_out, st, frac(dyn), task_docs, ctr_ws)
   switch (shape) {
-    case 5: return launch_f8x4<32, 4, true, kF8QW, 1, 2, kF8Waves, 0, kLd, kF8D, true, true>(
-        ix, Qb, Qs, B, lq, out, ld_out, st, frac(kScanDynFrac), task_docs, ctr_ws);
+    case kF8ShapeW8Q8: return F8X4(kF8W8Q8, 1, kScanDynFrac);
     // 4-wave workgroups (32-token / 3-deep, PF): 7 = 4 queries per wave, three
     // workgroups per CU (3 waves per SIMD); 8 = 8 queries per wave, two per CU
     // (2 waves per SIMD from independent barrier domains); 9 = 2 queries per
     // wave, two per CU
-    case 7:
-      if (B <= 16)   // one query group: non-temporal doc stream
-        return launch_f8x4<32, 3, true, 4, 3, 3, 4, 0, kLd, kF8D47, true, false, false, false, false, 0, 2>(
-            ix, Qb, Qs, B, lq, out, ld_out, st, frac(kF8DynSmall), task_docs, ctr_ws);
-      return launch_f8x4<32, 3, true, 4, 3, 3, 4, 0, kLd, kF8D47, true>(ix, Qb, Qs, B, lq, out, ld_out, st,
-                                                                       frac(kF8DynSmall), task_docs, ctr_ws);
-    case 8: return launch_f8x4<32, 3, true, 8, 2, 2, 4, 0, kLd, kF8D47, true>(ix, Qb, Qs, B, lq, out, ld_out, st,
-                                                                              frac(kF8DynSmall), task_docs, ctr_ws);
-    case 9:
-      if (B <= 8)    // one query group: non-temporal doc stream
-        return launch_f8x4<32, 3, true, 2, 2, 2, 4, 0, kLd, kF8D, true, false, false, false, false, 0, 2>(
-            ix, Qb, Qs, B, lq, out, ld_out, st, frac(kF8DynB8), task_docs, ctr_ws);
-      return launch_f8x4<32, 3, true, 2, 2, 2, 4, 0, kLd, kF8D, true>(ix, Qb, Qs, B, lq, out, ld_out, st,
-                                                                     frac(kF8DynB8), task_docs, ctr_ws);
+    case kF8ShapeW4Q4:
+      if (B <= 16) return F8X4(nt(kF8W4Q4), 3, kF8DynSmall);   // one query group: non-temporal doc stream
+      return F8X4(kF8W4Q4, 3, kF8DynSmall);
+    case kF8ShapeW4Q8: return F8X4(kF8W4Q8, 2, kF8DynSmall);
+    case kF8ShapeW4Q2:
+      if (B <= 8) return F8X4(nt(kF8W4Q2), 2, kF8DynB8);       // one query group: non-temporal doc stream
+      return F8X4(kF8W4Q2, 2, kF8DynB8);
     // 24 = 1 query per wave, two per CU (B = 3-4 without padded slots), non-temporal
-    case 24: return launch_f8x4<32, 3, true, 1, 2, 2, 4, 0, kLd, 1, true, false, false, false, false, 0, 2>(
-        ix, Qb, Qs, B, lq, out, ld_out, st, frac(kF8DynB8), task_docs, ctr_ws);
+    case kF8ShapeW4Q1: return F8X4(nt(kF8W4Q1), 2, kF8DynB8);
 #ifdef CBV2_LAB
-    case 1: return launch_f8x4<32, 3>(ix, Qb, Qs, B, lq, out, ld_out, st, frac(kScanDynFrac), task_docs, ctr_ws);
-    case 2: return launch_f8x4<64, 2>(ix, Qb, Qs, B, lq, out, ld_out, st, frac(kScanDynFrac), task_docs, ctr_ws);
-    case 3: return launch_f8x4<64, 3>(ix, Qb, Qs, B, lq, out, ld_out, st, frac(kScanDynFrac), task_docs, ctr_ws);
-    case 4: return launch_f8x4<128, 2>(ix, Qb, Qs, B, lq, out, ld_out, st, frac(kScanDynFrac), task_docs, ctr_ws);
-    case 6: return launch_f8x4<64, 2, true>(ix, Qb, Qs, B, lq, out, ld_out, st, frac(kScanDynFrac), task_docs, ctr_ws);
+    case kF8ShapeW8Q8NoPf: return F8X4(kW8Q8Plain, 1, kScanDynFrac);
+    case kF8ShapeTpi64N2: return F8X4(ring(kW8Q8Plain, 64, 2), 1, kScanDynFrac);
+    case kF8ShapeTpi64N3: return F8X4(ring(kW8Q8Plain, 64, 3), 1, kScanDynFrac);
+    case kF8ShapeTpi128N2: return F8X4(ring(kW8Q8Plain, 128, 2), 1, kScanDynFrac);
+    case kF8ShapeTpi64N2Pf: return F8X4(pf(ring(kW8Q8Plain, 64, 2)), 1, kScanDynFrac);
     // 12 = shape 5 before PAIR: one 32-token iteration per barrier, 3-deep ring
-    case 12: return launch_f8x4<32, 3, true, kF8QW, 1, 2, kF8Waves, 0, kLd, kF8D, true>(
-        ix, Qb, Qs, B, lq, out, ld_out, st, frac(kScanDynFrac), task_docs, ctr_ws);
-    case 10: return launch_f8x4<32, 3, true, 2, 3, 3, 4>(ix, Qb, Qs, B, lq, out, ld_out, st, frac(kScanDynFrac), task_docs, ctr_ws);
+    case kF8ShapeW8Q8Ring3: return F8X4(kF8W8Q8Ring3, 1, kScanDynFrac);
+    case kF8ShapeW4Q2x3: return F8X4((F8x4Cfg{.waves = 4, .qw = 2, .pf = true, .occ = 3}), 3, kScanDynFrac);
     // 11 = shape 5 as it was before the packed scales and D = 3 (round 2)
-    case 11: return launch_f8x4<32, 3, true, kF8QW, 1, 2, kF8Waves, 0, kLd, 1, false>(ix, Qb, Qs, B, lq, out, ld_out,
-                                                                                     st, frac(kScanDynFrac), task_docs, ctr_ws);
+    case kF8ShapeW8Q8Round2: return F8X4(pf(kW8Q8Plain), 1, kScanDynFrac);
     // 13 / 14 / 15 = shape 5 with SPREAD2 / SPLIT / both
-    case 13: return launch_f8x4<32, 4, true, kF8QW, 1, 2, kF8Waves, 0, kLd, kF8D, true, true, true, false>(
-        ix, Qb, Qs, B, lq, out, ld_out, st, frac(kScanDynFrac), task_docs, ctr_ws);
-    case 14: return launch_f8x4<32, 4, true, kF8QW, 1, 2, kF8Waves, 0, kLd, kF8D, true, true, false, true>(
-        ix, Qb, Qs, B, lq, out, ld_out, st, frac(kScanDynFrac), task_docs, ctr_ws);
-    case 15: return launch_f8x4<32, 4, true, kF8QW, 1, 2, kF8Waves, 0, kLd, kF8D, true, true, true, true>(
-        ix, Qb, Qs, B, lq, out, ld_out, st, frac(kScanDynFrac), task_docs, ctr_ws);
+    case kF8ShapeSpread2: return F8X4(spread2(kF8W8Q8), 1, kScanDynFrac);
+    case kF8ShapeSplit: return F8X4(split(kF8W8Q8), 1, kScanDynFrac);
+    case kF8ShapeSpread2Split: return F8X4(split(spread2(kF8W8Q8)), 1, kScanDynFrac);
     // 16 = QUAD: four 32-token iterations (a whole 128-token doc group) per barrier, 8 ring slots
-    case 16: return launch_f8x4<32, 8, true, kF8QW, 1, 2, kF8Waves, 0, kLd, kF8D, true, true, false, false, true>(
-        ix, Qb, Qs, B, lq, out, ld_out, st, frac(kScanDynFrac), task_docs, ctr_ws);
+    case kF8ShapeQuad: return F8X4(paired(kF8W8Q8Ring3, 4), 1, kScanDynFrac);
     // 17 / 18 = INVALID probes of shape 5: no per-MFMA fold / no epilogue row sums
-    case 17: return launch_f8x4<32, 4, true, kF8QW, 1, 2, kF8Waves, 0, kLd, kF8D, true, true, false, false, false, 1>(
-        ix, Qb, Qs, B, lq, out, ld_out, st, frac(kScanDynFrac), task_docs, ctr_ws);
-    case 18: return launch_f8x4<32, 4, true, kF8QW, 1, 2, kF8Waves, 0, kLd, kF8D, true, true, false, false, false, 2>(
-        ix, Qb, Qs, B, lq, out, ld_out, st, frac(kScanDynFrac), task_docs, ctr_ws);
+    case kF8ShapeProbeNoFold: return F8X4(probe(kF8W8Q8, 1), 1, kScanDynFrac);
+    case kF8ShapeProbeNoSums: return F8X4(probe(kF8W8Q8, 2), 1, kScanDynFrac);
 #endif
-    default: return launch_f8x4<32, 4, true, kF8QW, 1, 2, kF8Waves, 0, kLd, kF8D, true, true>(
-        ix, Qb, Qs, B, lq, out, ld_out, st, frac(kScanDynFrac), task_docs, ctr_ws);
+    default: return F8X4(kF8W8Q8, 1, kScanDynFrac);
   }
+#undef F8X4
 }
 
 // Fused top-k eligibility of a search, and the slot count its workspace
@@ -6851,7 +6861,8 @@ int scan_maxsim_timed(cbv2_index* ix, const void* Q, int32_t B, int32_t lq, floa
   if (timed && hipEventRecord(e0, st) != hipSuccess) return fail(CBV2_EHIP, "hipEventRecord failed");
   g_clock_probe = timed && ix->clock_on ? ix->clk : nullptr;
   const int rc = ix->dtype == CBV2_DTYPE_MXFP8
-                     ? scan_f8(ix, (const uint8_t*)Q, B, lq, out, ld_out, st, kF8DynAuto, kScanTaskDocs, 0, ctr_ws, ft)
+                     ? scan_f8(ix, (const uint8_t*)Q, B, lq, out, ld_out, st, kF8DynAuto, kScanTaskDocs, kF8ShapeAuto,
+                               ctr_ws, ft)
                      : scan_maxsim(ix, (const uint16_t*)Q, B, lq, out, ld_out, st, kDefaultScan, ctr_ws, ft, bm);
   g_clock_probe = nullptr;
   // the stop event is recorded even after a failed launch, so the reserved pair stays readable
@@ -7096,6 +7107,19 @@ int split_queries(cbv2_index* ix, const float* Q, int B, int lq, F32Ws* w, hipSt
 // most kRsSmallPairs (query, candidate) pairs, kRsPerWave beyond)
 constexpr int64_t kRsSmallPairs = 4096;
 constexpr int64_t kRsSplitGrid = 1024;   // workgroups per row of a split rescoring launch (grid-stride beyond)
+struct RescoreGrid { unsigned gx; bool two; };
+RescoreGrid rescore_grid(const cbv2_index* ix, int B, int64_t span) {
+  // workgroups per row: ~4k per launch, 256..1024 per row -- a row's pairs
+  // beyond that grid-stride (band at 1M docs, grid 1024 / 512 / 256: B=256
+  // 2.76 / 2.64 / 2.57 ms, B=16 0.247 / 0.238 / 0.225, B=1 39 / 40 / 41 us;
+  // profiles/r04w_grid_ab.jsonl)
+  const int64_t grid_auto = std::min<int64_t>(kRsSplitGrid, std::max<int64_t>(256, 4096 / std::max(B, 1)));
+  const int64_t grid_max = ix->rescore_grid > 0 ? ix->rescore_grid : grid_auto;
+  const unsigned gx = (unsigned)(span < grid_max ? span : grid_max);
+  // (long documents keep 4 waves: the 2-wave build of the long-doc pair
+  // carries its row maxima across blocks and spills; same bits either way)
+  return {gx, ix->ld == kLd && (int64_t)gx * B > 3LL * cu_count(ix->device)};
+}
 int launch_rescore(cbv2_index* ix, const F32Ws* w, int B, int lq, const int32_t* cand, const int32_t* count,
                    int64_t limit, int64_t ld_c, float* out, int64_t ld_out, hipStream_t st,
                    const int32_t* only_neg = nullptr, int pw = 0, uint32_t* lb_min = nullptr, int64_t c0 = 0,
@@ -7107,16 +7131,7 @@ int launch_rescore(cbv2_index* ix, const F32Ws* w, int B, int lq, const int32_t*
     int64_t span = limit - c0;   // (pairs [c0, min(count, limit)) of a row)
     if (fb_T != nullptr) span = std::max<int64_t>(span, std::min<int64_t>(ix->n, 256));   // the fallback's grid
     if (span < 1) span = 1;      // a row select runs in the row's (last) workgroup even with no pair to score
-    // workgroups per row: ~4k per launch, 256..1024 per row -- a row's pairs
-    // beyond that grid-stride (band at 1M docs, grid 1024 / 512 / 256: B=256
-    // 2.76 / 2.64 / 2.57 ms, B=16 0.247 / 0.238 / 0.225, B=1 39 / 40 / 41 us;
-    // profiles/r04w_grid_ab.jsonl)
-    const int64_t grid_auto = std::min<int64_t>(kRsSplitGrid, std::max<int64_t>(256, 4096 / std::max(B, 1)));
-    const int64_t grid_max = ix->rescore_grid > 0 ? ix->rescore_grid : grid_auto;
-    const unsigned gx = (unsigned)(span < grid_max ? span : grid_max);
-    // (long documents keep 4 waves: the 2-wave build of the long-doc pair
-    // carries its row maxima across blocks and spills; same bits either way)
-    const bool two = ix->ld == kLd && (int64_t)gx * B > 3LL * cu_count(ix->device);
+    const auto [gx, two] = rescore_grid(ix, B, span);
     auto kern = ix->ld != kLd ? rescore_split_kernel<true, 4>
                               : (two ? rescore_split_kernel<false, 2> : rescore_split_kernel<false, 4>);
     hipLaunchKernelGGL(kern, dim3(gx, (unsigned)B), dim3(two ? 128 : 256), 0, st, ix->tokens, ix->resid, ix->doclens,
@@ -7253,37 +7268,28 @@ int launch_stream_ids(cbv2_index* ix, const cbv2_filter* f, const uint16_t* Q, i
                       hipStream_t st) {
   const int64_t m = f->m;
   const int nq_groups = (B + QW - 1) / QW;
-  const int64_t target_waves = 4LL * cu_count(ix->device) * kDirectOversub;
-  int64_t n_chunks = target_waves / nq_groups;
-  if (n_chunks > m) n_chunks = m;
-  if (n_chunks < 1) n_chunks = 1;
-  const int64_t chunk_docs = (m + n_chunks - 1) / n_chunks;
-  n_chunks = (m + chunk_docs - 1) / chunk_docs;
+  const auto [n_chunks, chunk_docs] = chunk_split(m, 4LL * cu_count(ix->device) * kDirectOversub, nq_groups);
   const int64_t grid = ((int64_t)nq_groups * n_chunks + 3) / 4;
   if (grid > 0x7fffffff) return fail(CBV2_EUNSUPPORTED, "scan grid too large");
-  hipLaunchKernelGGL((maxsim_scan_stream_kernel<QW, 2, 4, kStreamSlots, false, false, true>), dim3((unsigned)grid),
-                     dim3(256), 0, st, ix->tokens, ix->doclens, m, Q, B, lq, out, m, chunk_docs, (int)ix->ld,
-                     (uint32_t*)nullptr, (int64_t)0, (uint32_t*)nullptr, (int64_t)0, f->ids);
+  constexpr StreamCfg C{.qw = QW, .aux = 2, .idx = true};
+  hipLaunchKernelGGL(maxsim_scan_stream_kernel<C>, dim3((unsigned)grid), dim3(256), 0, st, ix->tokens, ix->doclens, m,
+                     Q, B, lq, out, m, chunk_docs, (int)ix->ld, (uint32_t*)nullptr, (int64_t)0, (uint32_t*)nullptr,
+                     (int64_t)0, f->ids);
   return launch_check("maxsim_scan_stream_kernel (subset)");
 }
 
-template <int WAVES, int QW, int PER_CU, int TPI = 32, bool SPLITLOAD = false>
+template <Scan16x4Cfg C, int PER_CU>
 int launch_scan16x4_ids(cbv2_index* ix, const cbv2_filter* f, const uint16_t* Q, int B, int lq, float* out,
                         hipStream_t st) {
-  constexpr int QPB = WAVES * QW;
+  constexpr int QPB = C.waves * C.qw;
   const int64_t m = f->m;
   const int nq_groups = (B + QPB - 1) / QPB;
-  int64_t n_chunks = (int64_t)PER_CU * cu_count(ix->device) / nq_groups;   // never more workgroups than resident slots
-  if (n_chunks > m) n_chunks = m;
-  if (n_chunks < 1) n_chunks = 1;
-  const int64_t chunk_docs = (m + n_chunks - 1) / n_chunks;
-  n_chunks = (m + chunk_docs - 1) / chunk_docs;
+  const auto [n_chunks, chunk_docs] = chunk_split(m, (int64_t)PER_CU * cu_count(ix->device), nq_groups);
   if ((int64_t)nq_groups * n_chunks > 0x7fffffff) return fail(CBV2_EUNSUPPORTED, "scan grid too large");
-  hipLaunchKernelGGL((maxsim_scan16x4_kernel<WAVES, QW, 2, 2, false, TPI, 2, false, 0, SPLITLOAD, false, 0, kLd, 0, 0,
-                                             false, true>),
-                     dim3((unsigned)(nq_groups * n_chunks)), dim3(WAVES * 64), 0, st, ix->tokens, ix->doclens, m, Q, B,
-                     lq, out, m, chunk_docs, /*static_docs=*/m, (int*)nullptr, 0, (uint64_t*)nullptr, 0,
-                     (uint64_t*)nullptr, 0, 1, (uint32_t*)nullptr, (int64_t)0, (uint32_t*)nullptr, (int64_t)0, f->ids);
+  hipLaunchKernelGGL(maxsim_scan16x4_kernel<with_idx(C)>, dim3((unsigned)(nq_groups * n_chunks)), dim3(C.waves * 64),
+                     0, st, ix->tokens, ix->doclens, m, Q, B, lq, out, m, chunk_docs, /*static_docs=*/m, (int*)nullptr,
+                     0, (uint64_t*)nullptr, 0, (uint64_t*)nullptr, 0, 1, (uint32_t*)nullptr, (int64_t)0,
+                     (uint32_t*)nullptr, (int64_t)0, f->ids);
   return launch_check("maxsim_scan16x4_kernel (subset)");
 }
 
@@ -7292,10 +7298,10 @@ int scan_maxsim_subset(cbv2_index* ix, const cbv2_filter* f, const uint16_t* Q, 
   if (B <= kDirectMaxB)   // HBM-bound: only the listed docs' token tiles move
     return B == 1 ? launch_stream_ids<1>(ix, f, Q, B, lq, out, st) : launch_stream_ids<2>(ix, f, Q, B, lq, out, st);
   switch (pick_shape(kBf16Shapes, B)) {   // each listed doc is loaded once per query group
-    case kScan16x4W4Q1: return launch_scan16x4_ids<4, 1, 2>(ix, f, Q, B, lq, out, st);
-    case kScan16x4W4Q2: return launch_scan16x4_ids<4, 2, 2>(ix, f, Q, B, lq, out, st);
-    case kScan16x4W4: return launch_scan16x4_ids<4, 4, 2>(ix, f, Q, B, lq, out, st);
-    default: return launch_scan16x4_ids<8, 4, 1, 64, true>(ix, f, Q, B, lq, out, st);
+    case kScan16x4W4Q1: return launch_scan16x4_ids<kW4Q1, 2>(ix, f, Q, B, lq, out, st);
+    case kScan16x4W4Q2: return launch_scan16x4_ids<kW4Q2, 2>(ix, f, Q, B, lq, out, st);
+    case kScan16x4W4: return launch_scan16x4_ids<kW4, 2>(ix, f, Q, B, lq, out, st);
+    default: return launch_scan16x4_ids<kW8, 1>(ix, f, Q, B, lq, out, st);
   }
 }
 
@@ -7303,10 +7309,7 @@ int scan_maxsim_subset(cbv2_index* ix, const cbv2_filter* f, const uint16_t* Q, 
 // workgroup, all three products in the kernel) over the id list -- the same
 // list for every row (ld_c = 0), local ids (id_base 0).
 int rescore_subset(cbv2_index* ix, const cbv2_filter* f, const F32Ws* w, int B, int lq, float* out, hipStream_t st) {
-  const int64_t grid_auto = std::min<int64_t>(kRsSplitGrid, std::max<int64_t>(256, 4096 / std::max(B, 1)));
-  const int64_t grid_max = ix->rescore_grid > 0 ? ix->rescore_grid : grid_auto;
-  const unsigned gx = (unsigned)(f->m < grid_max ? f->m : grid_max);   // a row's pairs beyond the grid stride it
-  const bool two = (int64_t)gx * B > 3LL * cu_count(ix->device);
+  const auto [gx, two] = rescore_grid(ix, B, f->m);   // a row's pairs beyond the grid stride it
   auto kern = two ? rescore_split_kernel<false, 2> : rescore_split_kernel<false, 4>;
   hipLaunchKernelGGL(kern, dim3(gx, (unsigned)B), dim3(two ? 128 : 256), 0, st, ix->tokens, ix->resid, ix->doclens,
                      ix->n, (int64_t)0, w->qhi, w->qlo, lq, f->ids, (const int32_t*)nullptr, f->m, (int64_t)0, out,
@@ -7415,10 +7418,10 @@ int launch_stream_ragged(cbv2_index* ix, const cbv2_filter_batch* fb, const uint
                          int64_t M, hipStream_t st) {
   const int64_t grid = (fb->chunks + 3) / 4;
   if (grid < 1 || grid > 0x1fffffff) return fail(CBV2_EUNSUPPORTED, "scan grid too large");
-  hipLaunchKernelGGL((maxsim_scan_stream_kernel<1, 2, 4, kStreamSlots, false, false, true, true>), dim3((unsigned)grid),
-                     dim3(256), 0, st, ix->tokens, ix->doclens, (int64_t)0, Q, B, lq, out, M, fb->chunk_docs,
-                     (int)ix->ld, (uint32_t*)nullptr, (int64_t)0, (uint32_t*)nullptr, (int64_t)0,
-                     (const int32_t*)nullptr, fb->table);
+  constexpr StreamCfg C{.qw = 1, .aux = 2, .idx = true, .rag = true};
+  hipLaunchKernelGGL(maxsim_scan_stream_kernel<C>, dim3((unsigned)grid), dim3(256), 0, st, ix->tokens, ix->doclens,
+                     (int64_t)0, Q, B, lq, out, M, fb->chunk_docs, (int)ix->ld, (uint32_t*)nullptr, (int64_t)0,
+                     (uint32_t*)nullptr, (int64_t)0, (const int32_t*)nullptr, fb->table);
   return launch_check("maxsim_scan_stream_kernel (ragged)");
 }
 
@@ -7426,10 +7429,7 @@ int launch_stream_ragged(cbv2_index* ix, const cbv2_filter_batch* fb, const uint
 // (ld_c = M, count[b] = m_b out of the table, local ids: id_base 0).
 int rescore_ragged(cbv2_index* ix, const cbv2_filter_batch* fb, const F32Ws* w, int B, int lq, const int32_t* cand,
                    float* out, int64_t M, hipStream_t st) {
-  const int64_t grid_auto = std::min<int64_t>(kRsSplitGrid, std::max<int64_t>(256, 4096 / std::max(B, 1)));
-  const int64_t grid_max = ix->rescore_grid > 0 ? ix->rescore_grid : grid_auto;
-  const unsigned gx = (unsigned)(M < grid_max ? M : grid_max);   // a row's pairs beyond the grid stride it
-  const bool two = (int64_t)gx * B > 3LL * cu_count(ix->device);
+  const auto [gx, two] = rescore_grid(ix, B, M);   // a row's pairs beyond the grid stride it
   auto kern = two ? rescore_split_kernel<false, 2> : rescore_split_kernel<false, 4>;
   hipLaunchKernelGGL(kern, dim3(gx, (unsigned)B), dim3(two ? 128 : 256), 0, st, ix->tokens, ix->resid, ix->doclens,
                      ix->n, (int64_t)0, w->qhi, w->qlo, lq, cand, fb->table + fb_off_count(B), M, M, out, M,

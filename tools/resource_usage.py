@@ -12,6 +12,8 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from hybrid_rag_colbertv2_amd._build import STD  # noqa: E402
 
 
 def main():
@@ -20,7 +22,7 @@ def main():
     ap.add_argument("--src", default=os.path.join(ROOT, "hybrid-rag-colbertv2_amd", "csrc", "colbert_mi355x.hip"))
     ap.add_argument("-D", action="append", default=[])
     a = ap.parse_args()
-    cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-honor-nans", "-c",
+    cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", STD, "-fPIC", "-fno-honor-nans", "-c",
            "--offload-device-only", "-I", os.path.join(ROOT, "include"), a.src, "-o", "/tmp/_ru.o",
            "-Rpass-analysis=kernel-resource-usage"] + [f"-D{d}" for d in a.D]
     out = subprocess.run(cmd, capture_output=True, text=True).stderr

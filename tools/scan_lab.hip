@@ -299,6 +299,25 @@ template <int MODE>
 int launch_x(cbv2_index* ix, const uint16_t* Q, int B, int lq, float* out, int64_t ld, hipStream_t st) {
   return launch_scan<8, 4, 1>(scan16x_kernel<8, 4, MODE>, ix, Q, B, lq, out, ld, st, "scan16x_kernel");
 }
+
+// What a lab kind changes of a production shape (kW4Q1 .. kW8 and their
+// modifiers in the product source); kW8R1 / kW8Q2: the round-1 8-wave shapes,
+// every wave issuing its own LDS-DMA pieces.
+constexpr Scan16x4Cfg kW8R1{.waves = 8, .qw = 4, .nbuf = 2, .tpi = 64}, kW8Q2{.waves = 8, .qw = 2, .nbuf = 2, .tpi = 64};
+constexpr Scan16x4Cfg with_stamps(Scan16x4Cfg c) { return c.stamps = true, c; }
+constexpr Scan16x4Cfg ring(Scan16x4Cfg c, int tpi, int nbuf) { return c.tpi = tpi, c.nbuf = nbuf, c; }
+constexpr Scan16x4Cfg spread(Scan16x4Cfg c) { return c.spread = true, c; }
+constexpr Scan16x4Cfg arrive(Scan16x4Cfg c) { return c.arrive = true, c; }
+constexpr Scan16x4Cfg splitload(Scan16x4Cfg c, bool on) { return c.splitload = on, c; }
+constexpr Scan16x4Cfg probe(Scan16x4Cfg c, int p, int d) { return c.probe = p, c.d = d, c; }
+constexpr Scan16x4Cfg kmajor(Scan16x4Cfg c) { return c.morder = 1, c; }
+// stamps != null: the STAMPS build of the same shape (per-workgroup clock, start skew, tail)
+template <Scan16x4Cfg C, int PER_CU>
+int lab16x4(cbv2_index* ix, const uint16_t* q, int B, int lq, float* out, int64_t ld, hipStream_t st, float dyn_frac,
+            int task_docs, void* stamps) {
+  if (stamps == nullptr) return launch_scan16x4<C, PER_CU>(ix, q, B, lq, out, ld, st, dyn_frac, task_docs);
+  return launch_scan16x4<with_stamps(C), PER_CU>(ix, q, B, lq, out, ld, st, dyn_frac, task_docs, (uint64_t*)stamps);
+}
 }  // namespace
 
 // The production B > 16 scan with an explicit work split: dyn_frac of the
@@ -312,24 +331,24 @@ extern "C" int lab_scan16x4(cbv2_index* ix, const void* Q, int B, int lq, float*
   // D = 1/2/3 -> 73.3 / 76.3 / 76.1 % vs product 76.3 %; removed)
   //   kind 0 = production (64-token iterations, 2-deep ring: 142.5 -> 139.1 ms
   //   at 1M vs 32-token iterations with a 3-deep ring, which is kind 1)
-  if (kind == 1) return launch_scan16x4<8, 4, 1, 2, 3, false, 32>(ix, q, B, lq, out, ld, st, dyn_frac, task_docs);
+  if (kind == 1) return launch_scan16x4<ring(kW8R1, 32, 3), 1>(ix, q, B, lq, out, ld, st, dyn_frac, task_docs);
   // (kinds 2-5, round 1: one wave per SIMD, 4 waves x 8 queries, 163 vs 142 ms: removed)
   // mid-batch shapes (B = 16 / 64): 6 = production 4-wave x 4 queries (2 WGs/CU, 32-token ring),
   // 7 = 8 waves x 2 queries (one WG/CU, 64-token ring), 8 = 4 x 4 with 64-token iterations,
   // 9 = 8 waves x 2 queries, 32-token 3-deep ring
-  if (kind == 6) return launch_scan16x4<4, 4, 2, 2, 2, false, 32>(ix, q, B, lq, out, ld, st, dyn_frac, task_docs);
-  if (kind == 7) return launch_scan16x4<8, 2, 1, 2, 2, false, 64>(ix, q, B, lq, out, ld, st, dyn_frac, task_docs);
-  if (kind == 8) return launch_scan16x4<4, 4, 2, 2, 2, false, 64>(ix, q, B, lq, out, ld, st, dyn_frac, task_docs);
-  if (kind == 9) return launch_scan16x4<8, 2, 1, 2, 3, false, 32>(ix, q, B, lq, out, ld, st, dyn_frac, task_docs);
+  if (kind == 6) return launch_scan16x4<kW4, 2>(ix, q, B, lq, out, ld, st, dyn_frac, task_docs);
+  if (kind == 7) return launch_scan16x4<kW8Q2, 1>(ix, q, B, lq, out, ld, st, dyn_frac, task_docs);
+  if (kind == 8) return launch_scan16x4<ring(kW4, 64, 2), 2>(ix, q, B, lq, out, ld, st, dyn_frac, task_docs);
+  if (kind == 9) return launch_scan16x4<ring(kW8Q2, 32, 3), 1>(ix, q, B, lq, out, ld, st, dyn_frac, task_docs);
   // kind 10: production shape with the spread DMA issue (SPREAD); kind 11: its
   // phase-stamped build (STAMPS + SPREAD; the stamps buffer is required)
-  if (kind == 10) return launch_scan16x4<8, 4, 1, 2, 2, false, 64, 2, true>(ix, q, B, lq, out, ld, st, dyn_frac, task_docs);
+  if (kind == 10) return launch_scan16x4<spread(kW8R1), 1>(ix, q, B, lq, out, ld, st, dyn_frac, task_docs);
   if (kind == 11 && stamps != nullptr)
-    return launch_scan16x4<8, 4, 1, 2, 2, true, 64, 2, true>(ix, q, B, lq, out, ld, st, dyn_frac, task_docs,
-                                                             (uint64_t*)stamps);
+    return launch_scan16x4<with_stamps(spread(kW8R1)), 1>(ix, q, B, lq, out, ld, st, dyn_frac, task_docs,
+                                                          (uint64_t*)stamps);
   // kind 12: the B <= 16 production shape (kind 6) phase-stamped
   if (kind == 12 && stamps != nullptr)
-    return launch_scan16x4<4, 4, 2, 2, 2, true, 32>(ix, q, B, lq, out, ld, st, dyn_frac, task_docs, (uint64_t*)stamps);
+    return launch_scan16x4<with_stamps(kW4), 2>(ix, q, B, lq, out, ld, st, dyn_frac, task_docs, (uint64_t*)stamps);
   // kind 13: production shape (round 2: SPLITLOAD, waves 0-3 issue all LDS-DMA
   // pieces; kind 0 is the round-1 shape, every wave issuing its own); kind 14:
   // its phase-stamped build; kind 15 / 16: the fused top-k build (k = 100,
@@ -339,18 +358,16 @@ extern "C" int lab_scan16x4(cbv2_index* ix, const void* Q, int B, int lq, float*
   // 4288 | 111, issue 762 | 1599, compute 13211 | 16548; k14 wait 3919 | 116,
   // issue 1405 | 398, compute 12642 | 17459 (r02c)
   if (kind == 13)
-    return launch_scan16x4<8, 4, 1, 2, 2, false, 64, 2, false, 0, true>(ix, q, B, lq, out, ld, st, dyn_frac,
-                                                                        task_docs);
+    return launch_scan16x4<kW8, 1>(ix, q, B, lq, out, ld, st, dyn_frac, task_docs);
   if (kind == 14 && stamps != nullptr)
-    return launch_scan16x4<8, 4, 1, 2, 2, true, 64, 2, false, 0, true>(ix, q, B, lq, out, ld, st, dyn_frac,
-                                                                       task_docs, (uint64_t*)stamps);
+    return launch_scan16x4<with_stamps(kW8), 1>(ix, q, B, lq, out, ld, st, dyn_frac, task_docs, (uint64_t*)stamps);
   if (kind == 15 || kind == 16) {
     FusedTopk ft{(uint64_t*)out, 100, scan_chunks(ix, (B + 31) / 32, cu_count(ix->device)), 0};
     if ((int64_t)B * ft.max_slots * 100 * 8 > ld * (int64_t)B * 4) return -1;   // keys must fit the buffer
     if (kind == 15)
-      return launch_scan16x4<8, 4, 1, 2, 2, false, 64, 2, false, kFusedCap, false>(
+      return launch_scan16x4<fused(kW8R1), 1>(
           ix, q, B, lq, nullptr, 0, st, dyn_frac, task_docs, nullptr, nullptr, &ft);
-    return launch_scan16x4<8, 4, 1, 2, 2, false, 64, 2, false, kFusedCap, true>(
+    return launch_scan16x4<fused(kW8), 1>(
         ix, q, B, lq, nullptr, 0, st, dyn_frac, task_docs, nullptr, nullptr, &ft);
   }
   // kinds 17-22 (round 2): ARRIVE -- LDS landed/done counters instead of the
@@ -358,115 +375,83 @@ extern "C" int lab_scan16x4(cbv2_index* ix, const void* Q, int B, int lq, float*
   // 2-deep; 19: 32-token, 3-deep; 20: kind 17 phase-stamped; 21 / 22: the fused
   // top-k builds of 17 / 18 (k = 100, keys into `out`).
   if (kind == 17)
-    return launch_scan16x4<8, 4, 1, 2, 4, false, 32, 2, false, 0, true, true>(ix, q, B, lq, out, ld, st, dyn_frac,
-                                                                             task_docs);
+    return launch_scan16x4<arrive(ring(kW8, 32, 4)), 1>(ix, q, B, lq, out, ld, st, dyn_frac, task_docs);
   if (kind == 18)
-    return launch_scan16x4<8, 4, 1, 2, 2, false, 64, 2, false, 0, true, true>(ix, q, B, lq, out, ld, st, dyn_frac,
-                                                                             task_docs);
+    return launch_scan16x4<arrive(kW8), 1>(ix, q, B, lq, out, ld, st, dyn_frac, task_docs);
   if (kind == 19)
-    return launch_scan16x4<8, 4, 1, 2, 3, false, 32, 2, false, 0, true, true>(ix, q, B, lq, out, ld, st, dyn_frac,
-                                                                             task_docs);
+    return launch_scan16x4<arrive(ring(kW8, 32, 3)), 1>(ix, q, B, lq, out, ld, st, dyn_frac, task_docs);
   if (kind == 20 && stamps != nullptr)
-    return launch_scan16x4<8, 4, 1, 2, 4, true, 32, 2, false, 0, true, true>(ix, q, B, lq, out, ld, st, dyn_frac,
-                                                                            task_docs, (uint64_t*)stamps);
+    return launch_scan16x4<with_stamps(arrive(ring(kW8, 32, 4))), 1>(ix, q, B, lq, out, ld, st, dyn_frac, task_docs,
+                                                                     (uint64_t*)stamps);
   if (kind == 21 || kind == 22) {
     FusedTopk ft{(uint64_t*)out, 100, scan_chunks(ix, (B + 31) / 32, cu_count(ix->device)), 0};
     if ((int64_t)B * ft.max_slots * 100 * 8 > ld * (int64_t)B * 4) return -1;
     if (kind == 21)
-      return launch_scan16x4<8, 4, 1, 2, 4, false, 32, 2, false, kFusedCap, true, true>(
+      return launch_scan16x4<fused(arrive(ring(kW8, 32, 4))), 1>(
           ix, q, B, lq, nullptr, 0, st, dyn_frac, task_docs, nullptr, nullptr, &ft);
-    return launch_scan16x4<8, 4, 1, 2, 2, false, 64, 2, false, kFusedCap, true, true>(
+    return launch_scan16x4<fused(arrive(kW8)), 1>(
         ix, q, B, lq, nullptr, 0, st, dyn_frac, task_docs, nullptr, nullptr, &ft);
   }
   // kind 23: energy probe (INVALID scores) -- kind 13 with half the LDS read
   // bytes (odd tiles reuse the even tile's fragments), same MFMA stream
   if (kind == 23)
-    return launch_scan16x4<8, 4, 1, 2, 2, false, 64, 2, false, 0, true, false, 1>(ix, q, B, lq, out, ld, st, dyn_frac,
-                                                                                 task_docs);
+    return launch_scan16x4<probe(kW8, 1, 2), 1>(ix, q, B, lq, out, ld, st, dyn_frac, task_docs);
   // kind 24: energy probe (INVALID) -- kind 13 without doc streaming after the first fill
   if (kind == 24)
-    return launch_scan16x4<8, 4, 1, 2, 2, false, 64, 2, false, 0, true, false, 2>(ix, q, B, lq, out, ld, st, dyn_frac,
-                                                                                 task_docs);
+    return launch_scan16x4<probe(kW8, 2, 2), 1>(ix, q, B, lq, out, ld, st, dyn_frac, task_docs);
   // kind 25: kind 13 with the k-step-major MFMA order (iter4_full_kmajor: 8 live
   // accumulators, consecutive MFMAs share the doc fragment); bit-identical
   if (kind == 25)
-    return launch_scan16x4<8, 4, 1, 2, 2, false, 64, 2, false, 0, true, false, 0, kLd, 1>(ix, q, B, lq, out, ld, st,
-                                                                                         dyn_frac, task_docs);
+    return launch_scan16x4<kmajor(kW8), 1>(ix, q, B, lq, out, ld, st, dyn_frac, task_docs);
   // kind 26: the B <= 16 shape (kind 6) with the k-step-major MFMA order
   if (kind == 26)
-    return launch_scan16x4<4, 4, 2, 2, 2, false, 32, 2, false, 0, false, false, 0, kLd, 1>(ix, q, B, lq, out, ld, st,
-                                                                                          dyn_frac, task_docs);
+    return launch_scan16x4<kmajor(kW4), 2>(ix, q, B, lq, out, ld, st, dyn_frac, task_docs);
   // kind 27 / 28: the 4-wave shape with 2 queries per wave (8 per workgroup:
   // production kScan16x4W4Q2) / its phase-stamped build
   if (kind == 27)
-    return launch_scan16x4<4, 2, 2, 2, 2, false, 32>(ix, q, B, lq, out, ld, st, dyn_frac, task_docs);
+    return launch_scan16x4<kW4Q2, 2>(ix, q, B, lq, out, ld, st, dyn_frac, task_docs);
   if (kind == 28 && stamps != nullptr)
-    return launch_scan16x4<4, 2, 2, 2, 2, true, 32>(ix, q, B, lq, out, ld, st, dyn_frac, task_docs, (uint64_t*)stamps);
+    return launch_scan16x4<with_stamps(kW4Q2), 2>(ix, q, B, lq, out, ld, st, dyn_frac, task_docs, (uint64_t*)stamps);
   // kinds 29-32 (round 5, power probe): the one-group non-temporal mid-batch
   // shapes -- 29: 4 x 4 (B = 9-16, production kScan16x4W4Nt), 30: the same
   // with PROBE 3 (INVALID: the FLOPs on v_mfma_f32_32x32x16_bf16); 31 / 32:
   // 4 x 2 (B = 5-8) and its PROBE 3 build
   // stamps != null: the STAMPS build of the same shape (per-workgroup clock)
-#define LAB_MID(W, QW_, D_, PR)                                                                                  \
-  return stamps ? launch_scan16x4<W, QW_, 2, D_, 2, true, 32, 2, false, 0, false, false, PR, kLd, 0, 2>(            \
-                      ix, q, B, lq, out, ld, st, dyn_frac, task_docs, (uint64_t*)stamps, nullptr)                   \
-                : launch_scan16x4<W, QW_, 2, D_, 2, false, 32, 2, false, 0, false, false, PR, kLd, 0, 2>(           \
-                      ix, q, B, lq, out, ld, st, dyn_frac, task_docs, nullptr, nullptr)
-  if (kind == 29) LAB_MID(4, 4, 2, 0);
-  if (kind == 30) LAB_MID(4, 4, 0, 3);
-  if (kind == 31) LAB_MID(4, 2, 2, 0);
-  if (kind == 32) LAB_MID(4, 2, 1, 3);
-#undef LAB_MID
+#define LAB16X4(cfg, per_cu) lab16x4<cfg, per_cu>(ix, q, B, lq, out, ld, st, dyn_frac, task_docs, stamps)
+  if (kind == 29) return LAB16X4(nt(kW4), 2);
+  if (kind == 30) return LAB16X4(probe(nt(kW4), 3, 0), 2);
+  if (kind == 31) return LAB16X4(nt(kW4Q2), 2);
+  if (kind == 32) return LAB16X4(probe(nt(kW4Q2), 3, 1), 2);
   // kind 33 (round 6): the B <= 4 dense-doc production shape, 4 waves x 1
   // query, two per CU, non-temporal (kScan16x4W4Q1 without the folded keys);
   // stamps != null: its STAMPS build (per-workgroup clock, start skew, tail)
   if (kind == 33)
-    return stamps ? launch_scan16x4<4, 1, 2, 2, 2, true, 32, 2, false, 0, false, false, 0, kLd, 0, 2>(
-                        ix, q, B, lq, out, ld, st, dyn_frac, task_docs, (uint64_t*)stamps, nullptr)
-                  : launch_scan16x4<4, 1, 2, 2, 2, false, 32, 2, false, 0, false, false, 0, kLd, 0, 2>(
-                        ix, q, B, lq, out, ld, st, dyn_frac, task_docs, nullptr, nullptr);
+    return LAB16X4(nt(kW4Q1), 2);
   // kinds 34-36 (round 6): the B <= 4 shape with more doc bytes in flight per
   // CU -- 34: one workgroup per CU, 3-deep 32-token ring (96 KiB of LDS);
   // 35: one per CU, 64-token iterations, 2-deep (128 KiB); 36: one per CU,
   // ARRIVE (no per-iteration barrier, waves 0-1 load), 4-deep 32-token ring
   if (kind == 34)
-    return stamps ? launch_scan16x4<4, 1, 1, 2, 3, true, 32, 1, false, 0, false, false, 0, kLd, 0, 2>(
-                        ix, q, B, lq, out, ld, st, dyn_frac, task_docs, (uint64_t*)stamps, nullptr)
-                  : launch_scan16x4<4, 1, 1, 2, 3, false, 32, 1, false, 0, false, false, 0, kLd, 0, 2>(
-                        ix, q, B, lq, out, ld, st, dyn_frac, task_docs, nullptr, nullptr);
+    return LAB16X4(splitload(nt(one_wg(kW4Q1)), false), 1);
   if (kind == 35)
-    return stamps ? launch_scan16x4<4, 1, 1, 2, 2, true, 64, 1, false, 0, false, false, 0, kLd, 0, 2>(
-                        ix, q, B, lq, out, ld, st, dyn_frac, task_docs, (uint64_t*)stamps, nullptr)
-                  : launch_scan16x4<4, 1, 1, 2, 2, false, 64, 1, false, 0, false, false, 0, kLd, 0, 2>(
-                        ix, q, B, lq, out, ld, st, dyn_frac, task_docs, nullptr, nullptr);
+    return LAB16X4(ring(splitload(nt(one_wg(kW4Q1)), false), 64, 2), 1);
   if (kind == 36)
-    return stamps ? launch_scan16x4<4, 1, 1, 2, 4, true, 32, 1, false, 0, true, true, 0, kLd, 0, 2>(
-                        ix, q, B, lq, out, ld, st, dyn_frac, task_docs, (uint64_t*)stamps, nullptr)
-                  : launch_scan16x4<4, 1, 1, 2, 4, false, 32, 1, false, 0, true, true, 0, kLd, 0, 2>(
-                        ix, q, B, lq, out, ld, st, dyn_frac, task_docs, nullptr, nullptr);
+    return LAB16X4(arrive(ring(nt(one_wg(kW4Q1)), 32, 4)), 1);
   // kinds 37 / 38: kind 34 with SPLITLOAD (waves 0-1 issue every DMA piece) /
   // with a 4-deep ring (128 KiB of LDS, three iterations in flight)
   if (kind == 37)
-    return stamps ? launch_scan16x4<4, 1, 1, 2, 3, true, 32, 1, false, 0, true, false, 0, kLd, 0, 2>(
-                        ix, q, B, lq, out, ld, st, dyn_frac, task_docs, (uint64_t*)stamps, nullptr)
-                  : launch_scan16x4<4, 1, 1, 2, 3, false, 32, 1, false, 0, true, false, 0, kLd, 0, 2>(
-                        ix, q, B, lq, out, ld, st, dyn_frac, task_docs, nullptr, nullptr);
+    return LAB16X4(nt(one_wg(kW4Q1)), 1);
   if (kind == 38)
-    return stamps ? launch_scan16x4<4, 1, 1, 2, 4, true, 32, 1, false, 0, false, false, 0, kLd, 0, 2>(
-                        ix, q, B, lq, out, ld, st, dyn_frac, task_docs, (uint64_t*)stamps, nullptr)
-                  : launch_scan16x4<4, 1, 1, 2, 4, false, 32, 1, false, 0, false, false, 0, kLd, 0, 2>(
-                        ix, q, B, lq, out, ld, st, dyn_frac, task_docs, nullptr, nullptr);
+    return LAB16X4(ring(splitload(nt(one_wg(kW4Q1)), false), 32, 4), 1);
   // kinds 39 / 40: the B = 5-8 shape (4 x 2) at one workgroup per CU, 3- / 4-deep
   if (kind == 39)
-    return launch_scan16x4<4, 2, 1, 2, 3, false, 32, 1, false, 0, false, false, 0, kLd, 0, 2>(
-        ix, q, B, lq, out, ld, st, dyn_frac, task_docs, nullptr, nullptr);
+    return launch_scan16x4<splitload(nt(one_wg(kW4Q2)), false), 1>(ix, q, B, lq, out, ld, st, dyn_frac, task_docs);
   if (kind == 40)
-    return launch_scan16x4<4, 2, 1, 2, 4, false, 32, 1, false, 0, false, false, 0, kLd, 0, 2>(
-        ix, q, B, lq, out, ld, st, dyn_frac, task_docs, nullptr, nullptr);
+    return launch_scan16x4<ring(splitload(nt(one_wg(kW4Q2)), false), 32, 4), 1>(ix, q, B, lq, out, ld, st, dyn_frac,
+                                                                                 task_docs);
   // kind 41: the production B = 5-8 shape (4 x 2, two per CU, nt)
   if (kind == 41)
-    return launch_scan16x4<4, 2, 2, 2, 2, false, 32, 2, false, 0, false, false, 0, kLd, 0, 2>(
-        ix, q, B, lq, out, ld, st, dyn_frac, task_docs, nullptr, nullptr);
+    return launch_scan16x4<nt(kW4Q2), 2>(ix, q, B, lq, out, ld, st, dyn_frac, task_docs);
   // kind 42: the production dense B <= 2 scan WITH the block-max keys folded
   // in (the latency path's form; kind 37 is the same without them): the keys
   // zeroed by a memset inside the timed region (as the query split does in
@@ -481,14 +466,12 @@ extern "C" int lab_scan16x4(cbv2_index* ix, const void* Q, int B, int lq, float*
       bm_bytes = need;
     }
     if (hipMemsetAsync(bm, 0, need, st) != hipSuccess) return -3;
-    return launch_scan16x4<4, 1, 1, 2, 3, false, 32, 1, false, 0, true, false, 0, kLd, 0, 2, true>(
+    return launch_scan16x4<with_bmk(nt(one_wg(kW4Q1))), 1>(
         ix, q, B, lq, out, ld, st, dyn_frac, task_docs, nullptr, nullptr, nullptr, bm);
   }
   if (kind != 0) return -1;
-  if (stamps != nullptr)
-    return launch_scan16x4<8, 4, 1, 2, 2, true, 64>(ix, q, B, lq, out, ld, st, dyn_frac, task_docs,
-                                                    (uint64_t*)stamps);
-  return launch_scan16x4<8, 4, 1, 2, 2, false, 64>(ix, q, B, lq, out, ld, st, dyn_frac, task_docs, nullptr);
+  return LAB16X4(kW8R1, 1);
+#undef LAB16X4
 }
 
 // The B <= 2 direct scan with mult x the production chunk count (smaller
@@ -499,11 +482,7 @@ int lab_direct(cbv2_index* ix, const uint16_t* Q, int B, int lq, float* out, int
                int mult) {
   const int nq_groups = (B + QW - 1) / QW;
   const int64_t target_waves = 8LL * cu_count(ix->device) * mult;
-  int64_t n_chunks = target_waves / nq_groups;
-  if (n_chunks > ix->n) n_chunks = ix->n;
-  if (n_chunks < 1) n_chunks = 1;
-  const int64_t chunk_docs = (ix->n + n_chunks - 1) / n_chunks;
-  n_chunks = (ix->n + chunk_docs - 1) / chunk_docs;
+  const auto [n_chunks, chunk_docs] = chunk_split(ix->n, target_waves, nq_groups);
   const int64_t grid = ((int64_t)nq_groups * n_chunks + 3) / 4;
   hipLaunchKernelGGL((maxsim_scan_direct_kernel<QW, false>), dim3((unsigned)grid), dim3(256), 0, st, ix->tokens,
                      ix->doclens, ix->n, Q, B, lq, out, ld_out, chunk_docs, kLd);
@@ -547,26 +526,24 @@ extern "C" int lab_scan_f8(cbv2_index* ix, int variant, const void* Qbuf, int B,
   // 300 / 301 (round 6): the dense B <= 2 shape (24: 4 waves x 1 query, 3-deep
   // ring, nt) at ONE workgroup per CU, without / with SPLIT (waves 0-1 load);
   // 302: the production shape 24 (two per CU) at a 10 % tail
+  constexpr F8x4Cfg kOneWg{.waves = 4, .qw = 1, .pf = true, .occ = 1, .pqs = true, .aux = 2},
+      kOneWgSplit{.waves = 4, .qw = 1, .pf = true, .occ = 1, .pqs = true, .split = true, .aux = 2};
   if (variant == 300)
-    return launch_f8x4<32, 3, true, 1, 1, 1, 4, 0, kLd, 1, true, false, false, false, false, 0, 2>(
+    return launch_f8x4<kOneWg, 1>(
         ix, Qb, Qs, B, lq, out, ld, st, kF8DynB8, kScanTaskDocs, nullptr);
   if (variant == 301)
-    return launch_f8x4<32, 3, true, 1, 1, 1, 4, 0, kLd, 1, true, false, false, true, false, 0, 2>(
+    return launch_f8x4<kOneWgSplit, 1>(
         ix, Qb, Qs, B, lq, out, ld, st, kF8DynB8, kScanTaskDocs, nullptr);
   if (variant == 302)
-    return launch_f8x4<32, 3, true, 1, 2, 2, 4, 0, kLd, 1, true, false, false, false, false, 0, 2>(
+    return launch_f8x4<nt(kF8W4Q1), 2>(
         ix, Qb, Qs, B, lq, out, ld, st, 0.1f, kScanTaskDocs, nullptr);
   if (variant == 303)
-    return launch_f8x4<32, 3, true, 1, 1, 1, 4, 0, kLd, 1, true, false, false, true, false, 0, 2>(
+    return launch_f8x4<kOneWgSplit, 1>(
         ix, Qb, Qs, B, lq, out, ld, st, 0.1f, kScanTaskDocs, nullptr);
   if (variant >= 200 && variant < 300) {   // 200 + mult: the f8 direct scan (QW = 2) with mult x the resident waves
     constexpr int QW = 2;
     const int nq_groups = (B + QW - 1) / QW;
-    int64_t n_chunks = 8LL * cu_count(ix->device) * (variant - 200) / nq_groups;
-    if (n_chunks > ix->n) n_chunks = ix->n;
-    if (n_chunks < 1) n_chunks = 1;
-    const int64_t chunk_docs = (ix->n + n_chunks - 1) / n_chunks;
-    n_chunks = (ix->n + chunk_docs - 1) / chunk_docs;
+    const auto [n_chunks, chunk_docs] = chunk_split(ix->n, 8LL * cu_count(ix->device) * (variant - 200), nq_groups);
     const int64_t grid = ((int64_t)nq_groups * n_chunks + 3) / 4;
     hipLaunchKernelGGL(maxsim_scan_f8_direct_kernel<QW>, dim3((unsigned)grid), dim3(256), 0, st, ix->tokens,
                        ix->scales, ix->doclens, ix->n, Qb, Qs, B, lq, out, ld, chunk_docs);

@@ -19,6 +19,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from hybrid_rag_colbertv2_amd import synth  # noqa: E402
+from hybrid_rag_colbertv2_amd._build import STD  # noqa: E402
 from hybrid_rag_colbertv2_amd.index import ColbertIndex  # noqa: E402
 
 
@@ -56,7 +57,7 @@ def build():
         if not os.path.exists(lib) or os.path.getmtime(lib) < max(os.path.getmtime(src), os.path.getmtime(
                 os.path.join(ROOT, "hybrid-rag-colbertv2_amd", "csrc", "colbert_mi355x.hip"))):
             os.makedirs(os.path.dirname(lib), exist_ok=True)
-            subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
+            subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", STD, "-fPIC", "-shared",
                             "-fno-honor-nans", *defs, "-I", os.path.join(ROOT, "include"), src, "-o", lib],
                            check=True)
     with open(stamp, "w") as f:

@@ -18,6 +18,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from hybrid_rag_colbertv2_amd import synth  # noqa: E402
+from hybrid_rag_colbertv2_amd._build import STD  # noqa: E402
 from hybrid_rag_colbertv2_amd.index import ColbertIndex, _stream_ptr  # noqa: E402
 
 LAB = os.path.join(ROOT, "tools", "_lab", "libtopklab.so")
@@ -34,7 +35,7 @@ def main():
     a = ap.parse_args()
     if a.build or not os.path.exists(LAB):
         os.makedirs(os.path.dirname(LAB), exist_ok=True)
-        subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
+        subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", STD, "-fPIC", "-shared",
                         "-fno-honor-nans", "-I", os.path.join(ROOT, "include"),
                         os.path.join(ROOT, "tools", "topk_lab.hip"), "-o", LAB], check=True)
         if a.build:
