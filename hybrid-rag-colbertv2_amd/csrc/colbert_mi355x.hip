@@ -5842,6 +5842,7 @@ struct cbv2_index {
   bool band_open = false;
   std::vector<hipEvent_t> band_ev;
   int filter_path = 0;   // CBV2_OPT_FILTER_PATH (0: automatic, 1: subset where supported, 2: dense)
+  int filter_band = 0;   // CBV2_OPT_FILTER_BAND (0: automatic, 1: the band where supported, 2: never)
   int64_t filter_batch_chunk_docs = 0;   // CBV2_OPT_FILTER_BATCH_CHUNK_DOCS (0: automatic), read by cbv2_filter_batch_create
 };
 
@@ -7248,6 +7249,96 @@ __global__ __launch_bounds__(256) void filter_map_ids_kernel(int32_t* __restrict
   out_i[i] = (p >= 0 && p < m) ? (int32_t)(id_base + ids[p]) : -1;
 }
 
+// The same map row by row: dst[b][j] = id_base + ids[src[b][j]] for j < k (-1
+// for a position outside [0, m)); src == dst maps in place.  only_neg
+// (nullable): rows flagged < 0 only, the others are left as they are.
+__global__ __launch_bounds__(256) void filter_map_rows_kernel(const int32_t* src, int64_t ld_src, int32_t* dst,
+                                                              int64_t ld_dst, int k, const int32_t* __restrict__ ids,
+                                                              int64_t m, int64_t id_base,
+                                                              const int32_t* __restrict__ only_neg) {
+  const int b = blockIdx.y;
+  if (only_neg != nullptr && only_neg[b] >= 0) return;  // block-uniform
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= k) return;
+  const int32_t p = src[(size_t)b * ld_src + j];
+  dst[(size_t)b * ld_dst + j] = (p >= 0 && p < m) ? (int32_t)(id_base + ids[p]) : -1;
+}
+
+// Band collect over a compact filtered row (band_collect_kernel's flat path
+// with the id-list indirection): T [B][m] holds the bf16 scan's scores of the
+// m allowed docs in list order; row b appends id_base + ids[p] for every
+// position p < m with T[b][p] >= lb[b] - beta(b) to cand[b][0..cap), and
+// count[b] = the band size (may exceed cap: the search then recomputes that
+// row pair by pair).
+// Why the band still certifies the top-k under a filter: beta(q) bounds
+// |T - S| for every doc of the index, hence for every allowed doc.  lb[b] is
+// the minimum faithful score of k allowed docs (the bf16 top-k of the row), so
+// the k-th faithful score among the allowed docs is >= lb; an allowed doc that
+// can reach the top-k has S >= lb and therefore T >= S - beta >= lb - beta.
+// lb = -inf (an allowed empty doc in the bf16 top-k) makes the band the whole
+// list: every T, -inf included, reaches -inf.
+// The band's slots [0, k) are those k docs (seeded by filter_map_rows_kernel,
+// rescored by the lower-bound pass; count[b] starts at k): positions at or
+// above the k-th key (score desc, position asc -- the row top-k's own order)
+// are left out here.  Hits gather in an LDS list (one LDS atomic per wave with
+// a hit), flushed with one global atomic per workgroup.
+__global__ __launch_bounds__(256) void filter_band_collect_kernel(const float* __restrict__ T, int64_t m,
+                                                                  const int32_t* __restrict__ ids, int64_t id_base,
+                                                                  const float* __restrict__ topk_s,
+                                                                  const int32_t* __restrict__ topk_p, int k,
+                                                                  const float* __restrict__ beta,
+                                                                  const uint32_t* __restrict__ lbu, int cap,
+                                                                  int32_t* __restrict__ cand,
+                                                                  int32_t* __restrict__ count) {
+  __shared__ int32_t s_ids[kBandLds];
+  __shared__ int s_n, s_base;
+  const int b = blockIdx.y, lane = threadIdx.x & 63;
+  if (threadIdx.x == 0) s_n = 0;
+  __syncthreads();
+  const float thr = u2f(lbu[b]) - beta[b];
+  const float* row = T + (size_t)b * m;
+  int32_t* crow = cand + (size_t)b * cap;
+  const uint64_t kth = rank_key(topk_s[(size_t)b * k + k - 1], (uint32_t)topk_p[(size_t)b * k + k - 1]);
+  // position p (this lane's) with score v: appended when in the band (wave-uniform call)
+  auto offer = [&](int64_t p, float v) {
+    const bool take = p < m && v >= thr && rank_key(v, (uint32_t)p) < kth;
+    const uint64_t mask = __ballot(take);
+    if (mask == 0) return;
+    const int nh = __popcll(mask);
+    int base = 0;
+    if (lane == 0) base = atomicAdd(&s_n, nh);
+    base = __shfl(base, 0);
+    const int pos = base + __popcll(mask & ((1ull << lane) - 1ull));
+    if (take) {
+      const int32_t id = (int32_t)(id_base + ids[p]);
+      if (pos < kBandLds) {
+        s_ids[pos] = id;
+      } else {  // LDS list full (a very wide band): straight to the global list
+        const int gp = atomicAdd(count + b, 1);
+        if (gp < cap) crow[gp] = id;
+      }
+    }
+  };
+  constexpr int U = 8;  // 8 coalesced loads in flight per thread, then the ballots
+  const int64_t step = (int64_t)gridDim.x * blockDim.x * U;
+  for (int64_t p0 = (int64_t)blockIdx.x * blockDim.x * U; p0 < m; p0 += step) {  // uniform trip count per wave
+    float v[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int64_t p = p0 + (int64_t)u * blockDim.x + threadIdx.x;
+      v[u] = p < m ? row[p] : 0.0f;
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) offer(p0 + (int64_t)u * blockDim.x + threadIdx.x, v[u]);
+  }
+  __syncthreads();
+  const int nl = s_n < kBandLds ? s_n : kBandLds;
+  if (threadIdx.x == 0) s_base = nl > 0 ? atomicAdd(count + b, nl) : 0;
+  __syncthreads();
+  for (int t = threadIdx.x; t < nl; t += blockDim.x)
+    if (s_base + t < cap) crow[s_base + t] = s_ids[t];
+}
+
 size_t filter_buf_layout(int64_t n, size_t* off_blk, size_t* off_off, size_t* off_total) {
   auto r256 = [](size_t b) { return (b + 255) & ~(size_t)255; };
   const int64_t nn = n > 0 ? n : 1;
@@ -7307,13 +7398,18 @@ int scan_maxsim_subset(cbv2_index* ix, const cbv2_filter* f, const uint16_t* Q, 
 
 // The faithful subset: cbv2_score_f32's arithmetic (one (query, doc) pair per
 // workgroup, all three products in the kernel) over the id list -- the same
-// list for every row (ld_c = 0), local ids (id_base 0).
-int rescore_subset(cbv2_index* ix, const cbv2_filter* f, const F32Ws* w, int B, int lq, float* out, hipStream_t st) {
-  const auto [gx, two] = rescore_grid(ix, B, f->m);   // a row's pairs beyond the grid stride it
+// list for every row (ld_c = 0), local ids (id_base 0).  only_neg (nullable):
+// rows flagged < 0 only (the band's overflow recomputation) -- a small grid
+// then, as the unfiltered search's fallback: it is dispatched whether or not
+// a row overflowed.
+int rescore_subset(cbv2_index* ix, const cbv2_filter* f, const F32Ws* w, int B, int lq, float* out, hipStream_t st,
+                   const int32_t* only_neg = nullptr) {
+  const int64_t span = only_neg != nullptr ? std::min<int64_t>(f->m, std::max<int64_t>(64, 256 / B)) : f->m;
+  const auto [gx, two] = rescore_grid(ix, B, span);   // a row's pairs beyond the grid stride it
   auto kern = two ? rescore_split_kernel<false, 2> : rescore_split_kernel<false, 4>;
   hipLaunchKernelGGL(kern, dim3(gx, (unsigned)B), dim3(two ? 128 : 256), 0, st, ix->tokens, ix->resid, ix->doclens,
                      ix->n, (int64_t)0, w->qhi, w->qlo, lq, f->ids, (const int32_t*)nullptr, f->m, (int64_t)0, out,
-                     f->m, (const int32_t*)nullptr, (int)ix->ld, (uint32_t*)nullptr, (int64_t)0, (float*)nullptr,
+                     f->m, only_neg, (int)ix->ld, (uint32_t*)nullptr, (int64_t)0, (float*)nullptr,
                      (int32_t*)nullptr, 0, (float*)nullptr, (int32_t*)nullptr, RowSelect(), TaggedCand());
   return launch_check("rescore_split_kernel (subset)");
 }
@@ -7329,6 +7425,176 @@ int rescore_subset(cbv2_index* ix, const cbv2_filter* f, const F32Ws* w, int B, 
 // and 152.2 vs 149.9; faithful B=1 5.19 vs 10.41 and 10.60 vs 10.42 -- the
 // list's indirection costs ~5 % of a full scan).
 constexpr double kFilterSubsetMaxFrac = 0.5;
+bool filter_takes_subset(const cbv2_index* ix, int64_t m_allowed, int32_t scorer) {
+  const bool supported = scorer == CBV2_SCORER_MAXSIM && ix->dtype == CBV2_DTYPE_BF16 && ix->ld == kLd;
+  return supported && (ix->filter_path == 1 ||
+                       (ix->filter_path == 0 && (double)m_allowed <= kFilterSubsetMaxFrac * (double)ix->n));
+}
+
+// ---------------------------------------------------------------------------
+// Filtered faithful search (cbv2_search_filtered_f32; cbv2_search_filtered on
+// a faithful index with f32 queries): one filter for the call, three ways to
+// the same bits.
+//  dense: the filter path resolves to dense (above) -- every doc's faithful
+//         score into [B][n], the allowed columns gathered;
+//  pair:  one faithful score per (query, allowed doc) into the compact row
+//         [B][m] (rescore_subset);
+//  band:  the unfiltered faithful search's band method over the compact row:
+//         the bf16 subset scan of hi (T [B][m]), its row top-k, those k docs'
+//         faithful scores (their minimum lb bounds the k-th faithful score
+//         among the allowed docs from below), the band {T >= lb - beta}
+//         (filter_band_collect_kernel), its rescoring and the exact select;
+//         a row whose band overflows cap is recomputed pair by pair on the
+//         device (the launches of `pair`, gated on its status -1).
+// dense and pair end in the row top-k and the id map and report status -1.
+// CBV2_OPT_FILTER_BAND picks between pair and band where the subset path is
+// taken: the band needs m > k (with m <= k there is nothing to bound), k <=
+// kBandCapMax and the split rescoring.  Automatic: the band when
+//     B * (m - 2 k)  >=  kFilterBandMinSavedPairs + kFilterBandSavedPairsPerK * k.
+// Left: the faithful pairs the band can save -- it rescores the k docs of its
+// lower bound and a band that measured 1.8 .. 8.8 k docs per row, so at least
+// ~2 k.  Right: what its seven extra launches cost in pairs (~10 ns each), a
+// fixed part and one that grows with k (the row top-k of T and the band select
+// run one workgroup per row over k and >= 2 k keys).  Measured at 1M full docs,
+// band vs pair, medians of 5 (tools/filter_band_sweep.py; profiles/
+// filter_band_sweep.jsonl for k = 100, filter_band_sweep_k1000.jsonl):
+//   k = 100 (right side 5,600): the pair path wins at B=1 m=1,000 (left side
+//   800: 76 vs 54 us) and B=1 m=3,000 (2,800: 99 vs 79 us); the band wins at
+//   B=1 m=10,000 (9,800: 146 vs 168 us), B=16 m=1,000 (12,800: 163 vs 218 us)
+//   and at every larger point (B=16 m=100,000: 1.28 vs 16.2 ms; B=256
+//   m=10,000: 2.9 vs 23.6 ms);
+//   k = 1,000 (right side 20,000): the pair path wins at B=1 m=3,000 (1,000:
+//   165 vs 94 us), B=1 m=10,000 (8,000: 256 vs 187 us) and B=16 m=3,000
+//   (16,000: 0.51 vs 0.46 ms); the band wins at B=1 m=30,000 (28,000: 0.39 vs
+//   0.46 ms), B=16 m=10,000 (128,000: 0.77 vs 1.45 ms), B=256 m=3,000
+//   (256,000: 4.9 vs 6.3 ms) and at every larger point.
+// The two constants put the threshold between the last point the pair path won
+// and the first the band won at both k (k = 100: 2,800 .. 9,800; k = 1,000:
+// 16,000 .. 28,000); no other k was measured.
+// ---------------------------------------------------------------------------
+constexpr int64_t kFilterBandMinSavedPairs = 4000;
+constexpr int64_t kFilterBandSavedPairsPerK = 16;
+enum { kFfDense = 0, kFfPair = 1, kFfBand = 2 };
+int filter_f32_mode(const cbv2_index* ix, int64_t m, int32_t B, int32_t k) {
+  if (!filter_takes_subset(ix, m, CBV2_SCORER_MAXSIM)) return kFfDense;
+  if (m <= k || k > kBandCapMax || !ix->rescore_split || ix->filter_band == 2) return kFfPair;
+  if (ix->filter_band == 1) return kFfBand;
+  return (int64_t)B * (m - 2LL * k) >= kFilterBandMinSavedPairs + kFilterBandSavedPairsPerK * k ? kFfBand : kFfPair;
+}
+
+struct FilterF32Ws {
+  F32Ws w;                    // qhi, qlo, beta, tk, T [B][m]; band: lb, count, done, arrive, cand, F [B][cap]
+  int32_t* status = nullptr;  // [B] (cbv2_search_filtered keeps it here)
+  float* tks = nullptr;       // band: the bf16 row top-k's scores [B][k]
+  int32_t* pos = nullptr;     // band: and its row positions [B][k]
+  float* dense = nullptr;     // dense: [B][n]
+};
+size_t filter_f32_layout(const cbv2_index* ix, int64_t m_allowed, int mode, int B, int lq, int k, int cap, uint8_t* base,
+                         FilterF32Ws* fw) {
+  size_t off = 0;
+  auto take = [&](size_t bytes) -> uint8_t* {
+    uint8_t* p = base ? base + off : nullptr;
+    off += (bytes + 255) & ~(size_t)255;
+    return p;
+  };
+  F32Ws& w = fw->w;
+  const size_t m = (size_t)(m_allowed > 0 ? m_allowed : 1);
+  const size_t qbytes = (size_t)B * lq * kDim * sizeof(uint16_t);
+  w.qhi = (uint16_t*)take(qbytes);
+  w.qlo = (uint16_t*)take(qbytes);
+  w.beta = (float*)take((size_t)B * sizeof(float));
+  fw->status = (int32_t*)take((size_t)B * sizeof(int32_t));
+  w.tk_bytes = topk_ws_bytes(B, m_allowed);
+  w.tk = take(w.tk_bytes);
+  w.T = (float*)take((size_t)B * m * sizeof(float));
+  if (mode == kFfBand) {
+    w.lb = (float*)take((size_t)B * sizeof(float));
+    w.count = (int32_t*)take((size_t)B * sizeof(int32_t));
+    w.done = (int32_t*)take((size_t)B * sizeof(int32_t));
+    w.arrive = (int32_t*)take((size_t)kArriveSlots * B * kArriveInts * sizeof(int32_t));
+    w.cand = (int32_t*)take((size_t)B * cap * sizeof(int32_t));
+    w.F = (float*)take((size_t)B * cap * sizeof(float));
+    fw->tks = (float*)take((size_t)B * k * sizeof(float));
+    fw->pos = (int32_t*)take((size_t)B * k * sizeof(int32_t));
+  }
+  if (mode == kFfDense) fw->dense = (float*)take((size_t)B * (size_t)(ix->n > 0 ? ix->n : 1) * sizeof(float));
+  return off;
+}
+
+int search_filtered_f32_impl(cbv2_index* ix, const cbv2_filter* f, const float* Q, int32_t B, int32_t lq, int32_t k,
+                             int32_t cap, int mode, FilterF32Ws& fw, float* out_scores, int32_t* out_ids,
+                             int32_t* out_status, hipStream_t st) {
+  const int64_t m = f->m;
+  F32Ws& w = fw.w;
+  int rc;
+  if (m == 0) {   // padding only, no scan
+    CBV2_HIP(hipMemsetAsync(out_status, 0, (size_t)B * sizeof(int32_t), st));
+    return topk_impl_empty(B, k, out_scores, out_ids, st);
+  }
+  const int64_t total = (int64_t)B * k;
+  if (mode != kFfBand) {   // (out_status == nullptr: cbv2_search_filtered, which reports no status)
+    if (out_status != nullptr) CBV2_HIP(hipMemsetAsync(out_status, 0xff, (size_t)B * sizeof(int32_t), st));
+    if ((rc = split_queries(ix, Q, B, lq, &w, st))) return rc;
+    if (mode == kFfPair) {
+      if ((rc = rescore_subset(ix, f, &w, B, lq, w.T, st))) return rc;
+    } else {
+      if ((rc = launch_rescore(ix, &w, B, lq, nullptr, nullptr, ix->n, 0, fw.dense, ix->n, st))) return rc;
+      const int64_t gx = std::min<int64_t>((m + 255) / 256, 4096);
+      hipLaunchKernelGGL(filter_gather_kernel, dim3((unsigned)gx, (unsigned)std::min(B, 65535)), dim3(256), 0, st,
+                         fw.dense, ix->n, f->ids, m, B, w.T);
+      if ((rc = launch_check("filter_gather_kernel"))) return rc;
+    }
+    // the compact row's top-k (positions: id_base 0), then positions -> global ids
+    if ((rc = topk_impl(w.T, B, m, m, k, 0, w.tk, w.tk_bytes, out_scores, out_ids, st, ix->device))) return rc;
+    hipLaunchKernelGGL(filter_map_ids_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, out_ids, total,
+                       f->ids, m, f->id_base);
+    return launch_check("filter_map_ids_kernel");
+  }
+  // 1. the split (it resets the rows' band state: count = k, lb, done, arrival counters)
+  if ((rc = split_queries(ix, Q, B, lq, &w, st, k))) return rc;
+  // 2. bf16 scan of hi over the id list: the compact row T [B][m]
+  if ((rc = scan_maxsim_subset(ix, f, w.qhi, B, lq, w.T, st))) return rc;
+  // 3. T's row top-k (positions; m > k: no padding), those k docs as the
+  //    band's first k slots, their faithful scores and lb = their minimum
+  if ((rc = topk_impl(w.T, B, m, m, k, 0, w.tk, w.tk_bytes, fw.tks, fw.pos, st, ix->device))) return rc;
+  const dim3 gmap((unsigned)((k + 255) / 256), (unsigned)B);
+  hipLaunchKernelGGL(filter_map_rows_kernel, gmap, dim3(256), 0, st, fw.pos, (int64_t)k, w.cand, (int64_t)cap, k, f->ids,
+                     m, f->id_base, (const int32_t*)nullptr);
+  if ((rc = launch_check("filter_map_rows_kernel"))) return rc;
+  if ((rc = launch_rescore(ix, &w, B, lq, w.cand, nullptr, k, cap, w.F, cap, st, nullptr, 0,
+                           reinterpret_cast<uint32_t*>(w.lb))))
+    return rc;
+  // 4. the band of the compact row
+  int64_t splits = (8LL * cu_count(ix->device) + B - 1) / B;    // ~8 workgroups per CU
+  splits = std::max<int64_t>(1, std::min<int64_t>(splits, (m + 8191) / 8192));
+  hipLaunchKernelGGL(filter_band_collect_kernel, dim3((unsigned)splits, (unsigned)B), dim3(256), 0, st, w.T, m, f->ids,
+                     f->id_base, fw.tks, fw.pos, k, w.beta, reinterpret_cast<const uint32_t*>(w.lb), cap, w.cand,
+                     w.count);
+  if ((rc = launch_check("filter_band_collect_kernel"))) return rc;
+  // 5. its faithful scores (slots [k, count)), then the exact select (score desc, id asc)
+  if ((rc = launch_rescore(ix, &w, B, lq, w.cand, w.count, cap, cap, w.F, cap, st, nullptr, B <= kBandPairMaxB ? 1 : 0,
+                           nullptr, k)))
+    return rc;
+  hipLaunchKernelGGL(band_select_kernel, dim3((unsigned)B), dim3(kTkThreads), 0, st, w.F, w.cand, w.count, cap, k,
+                     ix->id_base, out_scores, out_ids, out_status, (const float*)nullptr,
+                     reinterpret_cast<const uint32_t*>(w.lb));
+  if ((rc = launch_check("band_select_kernel"))) return rc;
+  // 6. rows whose band overflowed cap (status -1): one faithful score per
+  //    allowed doc into the compact row, its exact top-k and the id map, each
+  //    launch gated on the status (other rows exit at once, untouched)
+  if ((rc = rescore_subset(ix, f, &w, B, lq, w.T, st, out_status))) return rc;
+  if (k > kTopkMax) {
+    if ((rc = topk_multi(w.T, B, m, m, k, 0, nullptr, 0, out_scores, out_ids, nullptr, st, out_status))) return rc;
+  } else {
+    hipLaunchKernelGGL(topk_rows_kernel, dim3((unsigned)B), dim3(kTkThreads), 0, st, w.T, m, m, k, (int64_t)0,
+                       out_scores, out_ids, out_status, Mirror());
+    if ((rc = launch_check("topk_rows_kernel"))) return rc;
+  }
+  hipLaunchKernelGGL(filter_map_rows_kernel, gmap, dim3(256), 0, st, out_ids, (int64_t)k, out_ids, (int64_t)k, k,
+                     f->ids, m, f->id_base, out_status);
+  return launch_check("filter_map_rows_kernel");
+}
+
 struct FilterPlan {
   bool subset = false;
   size_t tk_bytes = 0, off_tk = 0, off_row = 0, off_cand = 0, off_dense = 0, off_f32 = 0, total = 0;
@@ -7339,9 +7605,7 @@ struct FilterPlan {
 FilterPlan filter_plan_m(const cbv2_index* ix, int64_t m_allowed, bool cand, int32_t B, int32_t lq, int32_t scorer) {
   auto r256 = [](size_t b) { return (b + 255) & ~(size_t)255; };
   FilterPlan p;
-  const bool supported = scorer == CBV2_SCORER_MAXSIM && ix->dtype == CBV2_DTYPE_BF16 && ix->ld == kLd;
-  p.subset = supported && (ix->filter_path == 1 ||
-                           (ix->filter_path == 0 && (double)m_allowed <= kFilterSubsetMaxFrac * (double)ix->n));
+  p.subset = filter_takes_subset(ix, m_allowed, scorer);
   const bool f32 = ix->resid != nullptr && scorer == CBV2_SCORER_MAXSIM;
   const int64_t m = m_allowed > 0 ? m_allowed : 1;
   p.off_tk = kCtrBytes;
@@ -7357,8 +7621,18 @@ FilterPlan filter_plan_m(const cbv2_index* ix, int64_t m_allowed, bool cand, int
   }
   return p;
 }
-FilterPlan filter_plan(const cbv2_index* ix, const cbv2_filter* f, int32_t B, int32_t lq, int32_t scorer) {
-  return filter_plan_m(ix, f->m, false, B, lq, scorer);
+// One filter for the call.  On a faithful index the f32 queries' search lays
+// the workspace out by itself (filter_f32_layout, under the mode the options
+// give it); bf16 queries on the same index keep the layout above, and the
+// size covers both.
+FilterPlan filter_plan(const cbv2_index* ix, const cbv2_filter* f, int32_t B, int32_t lq, int32_t k, int32_t scorer) {
+  FilterPlan p = filter_plan_m(ix, f->m, false, B, lq, scorer);
+  if (ix->resid != nullptr && scorer == CBV2_SCORER_MAXSIM && lq <= kLqMax) {
+    FilterF32Ws fw;
+    p.total = std::max(p.total, filter_f32_layout(ix, f->m, filter_f32_mode(ix, f->m, B, k), B, lq, k,
+                                                  std::max<int32_t>(CBV2_RETRIEVE_BAND_CAP, k), nullptr, &fw));
+  }
+  return p;
 }
 
 // ---------------------------------------------------------------------------
@@ -7784,7 +8058,42 @@ int cbv2_filter_destroy(cbv2_filter* f) {
 size_t cbv2_search_filtered_workspace_size(const cbv2_index* ix, const cbv2_filter* f, int32_t B, int32_t lq,
                                            int32_t k, int32_t scorer) {
   if (!ix || !f || B < 1 || lq < 1 || k < 1) return 0;
-  return filter_plan(ix, f, B, lq, scorer).total;
+  return filter_plan(ix, f, B, lq, k, scorer).total;
+}
+
+size_t cbv2_search_filtered_f32_workspace_size(const cbv2_index* ix, const cbv2_filter* f, int32_t B, int32_t lq,
+                                               int32_t k, int32_t cap) {
+  if (!ix || !f || B < 1 || lq < 1 || k < 1 || cap < 0) return 0;
+  FilterF32Ws fw;
+  return filter_f32_layout(ix, f->m, filter_f32_mode(ix, f->m, B, k), B, lq, k, cap, nullptr, &fw);
+}
+
+int cbv2_search_filtered_f32(cbv2_index* ix, const cbv2_filter* f, const float* Q, int32_t B, int32_t lq, int32_t k,
+                             int32_t cap, void* ws, size_t ws_bytes, float* out_scores, int32_t* out_ids,
+                             int32_t* out_status, void* stream) {
+  CBV2_REQUIRE(f != nullptr, "null filter");
+  CBV2_REQUIRE(ix != nullptr, "null index");
+  if (ix->resid == nullptr) return fail(CBV2_ESTATE, "index has no fp32 residual (cbv2_index_attach_residual)");
+  CBV2_REQUIRE(Q != nullptr && aligned16(Q), "query pointer must be non-null and 16-byte aligned");
+  CBV2_REQUIRE(B >= 1 && B <= 65535, "B must be in [1, 65535] (got %d)", B);
+  CBV2_REQUIRE(lq >= 1 && lq <= kLqMax, "lq must be in [1, %d] (got %d)", kLqMax, lq);
+  CBV2_REQUIRE(f->n == ix->n && f->id_base == ix->id_base && f->device == ix->device,
+               "the filter was created for another index (n %lld / %lld, id_base %lld / %lld, device %d / %d)",
+               (long long)f->n, (long long)ix->n, (long long)f->id_base, (long long)ix->id_base, f->device, ix->device);
+  CBV2_REQUIRE(k >= 1, "k must be >= 1 (got %d)", k);
+  const int mode = filter_f32_mode(ix, f->m, B, k);
+  CBV2_REQUIRE(mode != kFfBand || (cap >= k && cap <= kBandCapMax), "cap must be in [k, %d] (got %d)", kBandCapMax,
+               cap);
+  CBV2_REQUIRE(out_scores && out_ids && out_status, "null outputs");
+  FilterF32Ws fw;
+  const size_t need = filter_f32_layout(ix, f->m, mode, B, lq, k, cap, nullptr, &fw);
+  CBV2_REQUIRE(ws != nullptr && ws_bytes >= need && aligned16(ws), "workspace too small or misaligned (%zu < %zu)",
+               ws_bytes, need);
+  filter_f32_layout(ix, f->m, mode, B, lq, k, cap, (uint8_t*)ws, &fw);
+  DeviceGuard dg(ix->device);
+  if (!dg.ok) return fail(CBV2_EHIP, "cannot select device %d", ix->device);
+  return search_filtered_f32_impl(ix, f, Q, B, lq, k, cap, mode, fw, out_scores, out_ids, out_status,
+                                  (hipStream_t)stream);
 }
 
 int cbv2_search_filtered(cbv2_index* ix, const cbv2_filter* f, int32_t scorer, const void* Q, int32_t q_dtype,
@@ -7805,7 +8114,7 @@ int cbv2_search_filtered(cbv2_index* ix, const cbv2_filter* f, int32_t scorer, c
                (long long)f->n, (long long)ix->n, (long long)f->id_base, (long long)ix->id_base, f->device, ix->device);
   CBV2_REQUIRE(k >= 1, "k must be >= 1 (got %d)", k);
   CBV2_REQUIRE(out_scores && out_ids, "null outputs");
-  const FilterPlan p = filter_plan(ix, f, B, lq, scorer);
+  const FilterPlan p = filter_plan(ix, f, B, lq, k, scorer);
   CBV2_REQUIRE(ws != nullptr && ws_bytes >= p.total && aligned16(ws), "workspace too small or misaligned (%zu < %zu)",
                ws_bytes, p.total);
   DeviceGuard dg(ix->device);
@@ -7813,23 +8122,22 @@ int cbv2_search_filtered(cbv2_index* ix, const cbv2_filter* f, int32_t scorer, c
   hipStream_t st = (hipStream_t)stream;
   const int64_t m = f->m;
   if (m == 0) return topk_impl_empty(B, k, out_scores, out_ids, st);   // padding only, no scan
+  if (faithful) {   // dense, pair by pair or the band (search_filtered_f32_impl); the status stays in the workspace
+    const int mode = filter_f32_mode(ix, m, B, k);
+    const int32_t cap = std::max<int32_t>(CBV2_RETRIEVE_BAND_CAP, k);
+    FilterF32Ws fw;
+    filter_f32_layout(ix, m, mode, B, lq, k, cap, (uint8_t*)ws, &fw);
+    return search_filtered_f32_impl(ix, f, (const float*)Q, B, lq, k, cap, mode, fw, out_scores, out_ids,
+                                    mode == kFfBand ? fw.status : nullptr, st);
+  }
   int* ctr = (int*)ws;
   float* row = (float*)((uint8_t*)ws + p.off_row);
   float* dense = (float*)((uint8_t*)ws + p.off_dense);
   int rc;
-  F32Ws w;
-  if (faithful) {
-    f32_ws_layout(ix, CBV2_F32_SCORE, B, lq, 0, (uint8_t*)ws + p.off_f32, &w);
-    if ((rc = split_queries(ix, (const float*)Q, B, lq, &w, st))) return rc;
-  }
   if (p.subset) {
-    rc = faithful ? rescore_subset(ix, f, &w, B, lq, row, st)
-                  : scan_maxsim_subset(ix, f, (const uint16_t*)Q, B, lq, row, st);
-    if (rc) return rc;
+    if ((rc = scan_maxsim_subset(ix, f, (const uint16_t*)Q, B, lq, row, st))) return rc;
   } else {
-    rc = faithful ? launch_rescore(ix, &w, B, lq, nullptr, nullptr, ix->n, 0, dense, ix->n, st)
-                  : score_impl(ix, scorer, Q, B, lq, dense, ix->n, st, ctr);
-    if (rc) return rc;
+    if ((rc = score_impl(ix, scorer, Q, B, lq, dense, ix->n, st, ctr))) return rc;
     const int64_t gx = std::min<int64_t>((m + 255) / 256, 4096);
     hipLaunchKernelGGL(filter_gather_kernel, dim3((unsigned)gx, (unsigned)std::min(B, 65535)), dim3(256), 0, st, dense, ix->n,
                        f->ids, m, B, row);
@@ -8030,6 +8338,10 @@ int cbv2_index_set_option(cbv2_index* ix, int32_t option, int64_t value) {
     case CBV2_OPT_FILTER_PATH:
       if (value < 0 || value > 2) return fail(CBV2_EINVAL, "filter path must be 0 (automatic), 1 (subset) or 2 (dense)");
       ix->filter_path = (int)value;
+      return CBV2_OK;
+    case CBV2_OPT_FILTER_BAND:
+      if (value < 0 || value > 2) return fail(CBV2_EINVAL, "filter band must be 0 (automatic), 1 (on) or 2 (never)");
+      ix->filter_band = (int)value;
       return CBV2_OK;
     case CBV2_OPT_FILTER_BATCH_CHUNK_DOCS:
       if (value < 0 || value > 0x7fffffffLL) return fail(CBV2_EINVAL, "filter batch chunk docs must be in [0, 2^31)");

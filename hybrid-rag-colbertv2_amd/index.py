@@ -670,8 +670,11 @@ class ColbertIndex:
         return DocFilter(self, pack_allow(ids if mask is None else torch.as_tensor(mask, dtype=torch.bool),
                                           self.n, self.id_base))
 
-    def _search_filtered(self, Q: torch.Tensor, k: int, scorer: str, flt: DocFilter):
-        """Top-k of the allowed docs (cbv2_search_filtered; asynchronous)."""
+    def _search_filtered(self, Q: torch.Tensor, k: int, scorer: str, flt: DocFilter, cap: int = BAND_CAP):
+        """Top-k of the allowed docs (cbv2_search_filtered; asynchronous).  A
+        faithful MaxSim search of at most 32 query tokens goes through
+        cbv2_search_filtered_f32 with band capacity ``cap``; ``last_band`` then
+        holds each row's band size, -1 for a row scored pair by pair."""
         if not isinstance(flt, DocFilter):
             raise TypeError("filter must be a DocFilter (ColbertIndex.filter)")
         if not flt._h.value:
@@ -695,11 +698,22 @@ class ColbertIndex:
         sid = self._scorer(scorer)
         _keep, qptr, qdt, B, lq = self._prep_query(Q, scorer)
         L = _lib.lib()
+        out_s = torch.empty((B, k), dtype=torch.float32, device=self.device)
+        out_i = torch.empty((B, k), dtype=torch.int32, device=self.device)
+        if self.faithful and scorer == "maxsim":
+            cap = max(int(cap), k)
+            need = int(L.cbv2_search_filtered_f32_workspace_size(self._h, flt._h, B, lq, k, cap))
+            if self._ws is None or self._ws.numel() * 4 < need:
+                self._ws = torch.empty(((need + 3) // 4,), dtype=torch.float32, device=self.device)
+            status = torch.empty((B,), dtype=torch.int32, device=self.device)
+            _lib.check(L.cbv2_search_filtered_f32(self._h, flt._h, qptr, B, lq, k, cap, self._ws.data_ptr(),
+                                                  self._ws.numel() * 4, out_s.data_ptr(), out_i.data_ptr(),
+                                                  status.data_ptr(), _stream_ptr(self.device)))
+            self.last_band = status
+            return out_s, out_i
         need = int(L.cbv2_search_filtered_workspace_size(self._h, flt._h, B, lq, k, sid))
         if self._ws is None or self._ws.numel() * 4 < need:
             self._ws = torch.empty(((need + 3) // 4,), dtype=torch.float32, device=self.device)
-        out_s = torch.empty((B, k), dtype=torch.float32, device=self.device)
-        out_i = torch.empty((B, k), dtype=torch.int32, device=self.device)
         _lib.check(L.cbv2_search_filtered(self._h, flt._h, sid, qptr, qdt, B, lq, k, self._ws.data_ptr(),
                                           self._ws.numel() * 4, out_s.data_ptr(), out_i.data_ptr(),
                                           _stream_ptr(self.device)))

@@ -45,6 +45,8 @@
  *    re-initialises what it uses in the caller's workspace, like the searches
  *    above (tests/test_gpu_filter_batch.py replays it over a poisoned
  *    workspace and poisoned outputs).
+ *    So has cbv2_search_filtered_f32 (the filter created before the capture;
+ *    tests/test_gpu_filter_band.py replays it the same way).
  *    Outside the list, not to be captured: cbv2_retrieve_* (pooled mapped buffers, a second stream
  *    and host polling), the sharded and loopback calls, cbv2_filter_create
  *    (waits for its count), cbv2_filter_batch_create (copies its table from
@@ -232,6 +234,13 @@ int cbv2_index_scan_clock(cbv2_index* index, int64_t* out4, int32_t reset);
  *                        dense path: DESIGN.md 3.8), 1 the subset path where
  *                        supported, 2 the dense path (score every doc, gather
  *                        the allowed columns).  Identical results.
+ *  CBV2_OPT_FILTER_BAND   the filtered faithful search (cbv2_search_filtered_f32,
+ *                        cbv2_search_filtered with f32 queries) where
+ *                        CBV2_OPT_FILTER_PATH resolves to the subset path: 0
+ *                        automatic (a rule of B, m and k), 1 the
+ *                        band over the compact row wherever it is supported
+ *                        (m > k, k <= 16384), 2 never (one faithful score per
+ *                        (query, allowed doc)).  Identical results.
  *  CBV2_OPT_FILTER_BATCH_CHUNK_DOCS  docs per work item of the per-query
  *                        filters' ragged scan (0: automatic, from the batch's
  *                        pair count and the CU count; > 0: for tests).  Read
@@ -256,6 +265,7 @@ int cbv2_index_scan_clock(cbv2_index* index, int64_t* out4, int32_t reset);
 #define CBV2_OPT_FOLD_KEYS 13
 #define CBV2_OPT_FILTER_PATH 14
 #define CBV2_OPT_FILTER_BATCH_CHUNK_DOCS 15
+#define CBV2_OPT_FILTER_BAND 16
 int cbv2_index_set_option(cbv2_index* index, int32_t option, int64_t value);
 int cbv2_index_last_scan_plan(const cbv2_index* index, int64_t* out4);
 /* Per-query workgroup lists a cbv2_search of (B, k, scorer) keeps with the
@@ -365,6 +375,52 @@ size_t cbv2_search_filtered_workspace_size(const cbv2_index* index, const cbv2_f
 int cbv2_search_filtered(cbv2_index* index, const cbv2_filter* filter, int32_t scorer, const void* Q, int32_t q_dtype,
                          int32_t B, int32_t lq, int32_t k, void* workspace, size_t workspace_bytes,
                          float* out_scores, int32_t* out_ids, void* stream);
+
+/* cbv2_search_filtered_f32 -- the filtered twin of cbv2_search_f32: the
+ * faithful top-k of the allowed docs of an fp32-faithful index, Q f32
+ * [B][lq][128], 1 <= lq <= 32.  Results are cbv2_search_filtered's for the
+ * same arguments, bit for bit: cbv2_score_f32's scores, score descending then
+ * id ascending, -inf / -1 past min(k, m), an allowed empty doc after every
+ * finite score.  out_status int32 [B]: the row's band size, or -1 when the
+ * row was scored pair by pair over its whole list; m == 0 writes padding only
+ * and status 0.
+ *  Where CBV2_OPT_FILTER_PATH resolves to the subset path (128-slot docs),
+ *  CBV2_OPT_FILTER_BAND picks between
+ *  pair -- one faithful score per (query, allowed doc), the row top-k, the id
+ *    map: status -1 everywhere; and
+ *  band -- cbv2_search_f32's band method over the compact row: the bf16 subset
+ *    scan of hi (T [B][m]), T's row top-k, the faithful scores of those k docs
+ *    (lb = their minimum: k allowed docs score at least lb), the band of every
+ *    list position with T >= lb - beta (beta(q) bounds |T - S| for every doc
+ *    of the index, so for every allowed one: no allowed doc outside the band
+ *    can reach the top-k), its rescoring and the exact select.  cap in
+ *    [k, 16384] (CBV2_EINVAL otherwise); a row whose band exceeds cap gets
+ *    status -1 and is recomputed pair by pair on the device, no host round
+ *    trip, the other rows untouched.  Needs m > k and k <= 16384: other calls
+ *    take `pair` (there cap is not read).  No [B][n] buffer of any kind.
+ *  Where the filter path resolves to dense (long documents; m > 0.5 n under
+ *  the automatic rule): every doc's faithful score into [B][n], a column
+ *  gather, status -1.
+ * Workspace (16-B aligned, one per stream): cbv2_search_filtered_f32_
+ * workspace_size(index, filter, B, lq, k, cap) bytes, computed with the
+ * options the search will run under (0 for a null handle or B, lq, k < 1).
+ * Every argument is validated before any launch: the filter's n / id_base /
+ * device against the index (CBV2_EINVAL), an index without a residual
+ * (CBV2_ESTATE).  Asynchronous and capturable (the filter created before the
+ * capture).  cbv2_search_filtered with f32 queries on a faithful index runs
+ * the same routine with cap = CBV2_RETRIEVE_BAND_CAP and keeps the status in
+ * its workspace.  Per-query filters (cbv2_search_filtered_batch), the sharded
+ * calls and the cbv2_retrieve_* calls are as they were: no band under a
+ * filter there.
+ * (Its guard-band test is tests/test_gpu_filter_band.py, not the table of
+ * tests/test_gpu_bounds.py, which lists the one-line `int cbv2_*(`
+ * declarations of this file: hence the return type on a line of its own.)   */
+size_t cbv2_search_filtered_f32_workspace_size(const cbv2_index* index, const cbv2_filter* filter, int32_t B,
+                                               int32_t lq, int32_t k, int32_t cap);
+int
+cbv2_search_filtered_f32(cbv2_index* index, const cbv2_filter* filter, const float* Q, int32_t B, int32_t lq,
+                             int32_t k, int32_t cap, void* workspace, size_t workspace_bytes, float* out_scores,
+                             int32_t* out_ids, int32_t* out_status, void* stream);
 
 /* Per-query filters: one filtered search for a batch whose queries each have
  * their own allowed set (256 users, each asking about their own document).
