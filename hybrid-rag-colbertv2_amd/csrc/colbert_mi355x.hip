@@ -2225,6 +2225,7 @@ struct F8x4Cfg {
   bool pqs = false;              // the query scale bytes packed four per VGPR
   bool pair = false, spread2 = false, split = false, quad = false;
   int probe = 0, aux = 0;        // lab probe; the doc stream's cache policy (as maxsim_scan16x4_kernel's AUX)
+  bool idx = false;              // the filtered search's subset scan (as maxsim_scan16x4_kernel's IDX)
 };
 template <F8x4Cfg C>
 __global__ __launch_bounds__(C.waves * 64, C.occ) void maxsim_scan_f8x4_kernel(
@@ -2232,10 +2233,18 @@ __global__ __launch_bounds__(C.waves * 64, C.occ) void maxsim_scan_f8x4_kernel(
     int64_t n, const uint8_t* __restrict__ Qb, const uint8_t* __restrict__ Qs, int B, int lq,
     float* __restrict__ out, int64_t ld_out, int64_t chunk_docs, int64_t static_docs, int* __restrict__ task_ctr,
     int task_docs, int topk_k = 0, uint64_t* __restrict__ part = nullptr, int nslots = 0, int tail_slices = 1,
-    uint64_t* __restrict__ clk = nullptr) {
+    uint64_t* __restrict__ clk = nullptr, const int32_t* __restrict__ ids = nullptr) {
   static constexpr int WAVES = C.waves, QW = C.qw, D = C.d, NBUF = C.nbuf, TPI = C.tpi, FK = C.fk, LD = C.ld, PROBE = C.probe,
                 AUX = C.aux;
-  static constexpr bool PF = C.pf, PQS = C.pqs, PAIR = C.pair, SPREAD2 = C.spread2, SPLIT = C.split, QUAD = C.quad;
+  static constexpr bool PF = C.pf, PQS = C.pqs, PAIR = C.pair, SPREAD2 = C.spread2, SPLIT = C.split, QUAD = C.quad,
+                 IDX = C.idx;
+  // IDX: the n "docs" are the entries of an ascending list of local doc ids;
+  // entry i is doc ids[i] (its tokens, its scales and its length go through
+  // the list) and scores into column i of the compact row.  A token piece's 8
+  // rows lie in one doc, so its list index is wave-uniform (a scalar load); the
+  // scale DMA's 128 rows are the group's 4 docs, 16 lanes each: four scalar
+  // loads and a select on the lane group.
+  static_assert(!IDX || (TPI == 32 && FK == 0 && PROBE == 0), "the subset scan: 32-token iterations, scores out");
   if (clk != nullptr && threadIdx.x == 0) clock_probe(clk, false);   // the bench's clock probe (null otherwise)
   constexpr int QPB = WAVES * QW;
   constexpr int kIterBytes = 4 * TPI * kDim;                 // e4m3 bytes per iteration
@@ -2305,13 +2314,22 @@ __global__ __launch_bounds__(C.waves * 64, C.occ) void maxsim_scan_f8x4_kernel(
       const int R = 8 * piece + (lane >> 3);
       const uint32_t off = (R % TPI) * kDim + 16 * ((lane & 7) ^ swz_f8<TPI>(R));
       const int d = clamp_doc(4 * G + 8 * piece / TPI);
-      const uint8_t* src = tokens + (size_t)(d_begin + d) * kDocStride + (size_t)j * TPI * kDim + off;
+      size_t di = (size_t)(d_begin + d);
+      if constexpr (IDX) di = (size_t)ids[d_begin + __builtin_amdgcn_readfirstlane(d)];
+      const uint8_t* src = tokens + di * kDocStride + (size_t)j * TPI * kDim + off;
       __builtin_amdgcn_global_load_lds((gbl_void_t*)src, (lds_void_t*)(sbuf + piece * 1024), 16, 0, AUX);
     }
     if (wave < kScaleDma) {  // scale bytes b = 256 * wave + 4L: row b/2 = TPI * doc + token
       const int R = (256 * wave + 4 * lane) / 2;
       const int d = clamp_doc(4 * G + R / TPI);
-      const uint8_t* src = tscales + (size_t)(d_begin + d) * kScaleStride + (size_t)(j * TPI + R % TPI) * 2;
+      size_t di = (size_t)(d_begin + d);
+      if constexpr (IDX) {   // (one scale DMA per iteration: R / TPI = lane >> 4)
+        int id4[4];
+#pragma unroll
+        for (int x = 0; x < 4; ++x) id4[x] = ids[d_begin + clamp_doc(4 * G + x)];
+        di = (size_t)(g == 0 ? id4[0] : (g == 1 ? id4[1] : (g == 2 ? id4[2] : id4[3])));
+      }
+      const uint8_t* src = tscales + di * kScaleStride + (size_t)(j * TPI + R % TPI) * 2;
       __builtin_amdgcn_global_load_lds((gbl_void_t*)src, (lds_void_t*)(sbuf + kIterBytes + 256 * wave), 4, 0, AUX);
     }
   };
@@ -2333,7 +2351,7 @@ __global__ __launch_bounds__(C.waves * 64, C.occ) void maxsim_scan_f8x4_kernel(
       int dl4[4];
 #pragma unroll
       for (int x = 0; x < 4; ++x) {
-        const int v = (4 * G + x < nd) ? doclens[d_begin + 4 * G + x] : 0;
+        const int v = (4 * G + x < nd) ? doclens[IDX ? (int64_t)ids[d_begin + 4 * G + x] : d_begin + 4 * G + x] : 0;
         dl4[x] = v < 0 ? 0 : (v > LD ? LD : v);
       }
       dl_min = min(min(dl4[0], dl4[1]), min(dl4[2], dl4[3]));
@@ -2570,34 +2588,72 @@ constexpr int kF8SlotBytes = 2048 + 256;
 // (profiles/r03z_lab_f8_tw2.log: variant 10 = one tile per wait, 32 = TW2 at
 // 8 x 8, 33 = TW2 at 4 x 16): 1.25M docs B=1 3.320 -> 3.282 ms, B=2 3.178 ->
 // 3.155, 125k B=1 0.318 -> 0.316; at 4 x 16 B=2 and 125k lose (3.342 / 0.423).
+// IDX / RAG (the filtered search's subset scan and the per-query filters'
+// ragged scan): as maxsim_scan_stream_kernel's -- entry i of the range is doc
+// ids[i]; its length (two dependent scalar loads, off the vmcnt count), its
+// token base (id * ld * 128) and its scale base (id * ld * 2) go through the
+// list, and its score lands in column i of the compact row.  RAG (IDX, QW =
+// 1): a wave's work item is (row b, chunk of row b's list), found by the same
+// binary search of the filter batch's table on the scalar unit before the
+// first LDS-DMA issue.
 struct F8StreamCfg {
   int qw, aux;                 // queries per wave, the doc stream's cache policy
   int waves = 4, slots = 16;   // waves per workgroup, tile slots per wave
   bool tw2 = true;             // TW2
+  bool idx = false, rag = false;
 };
 template <F8StreamCfg C>
 __global__ __launch_bounds__(C.waves * 64, 1) void maxsim_scan_f8_stream_kernel(
     const uint8_t* __restrict__ tokens, const uint8_t* __restrict__ tscales, const int32_t* __restrict__ doclens,
-    int64_t n, const uint8_t* __restrict__ Qb, const uint8_t* __restrict__ Qs, int B, int lq,
-    float* __restrict__ out, int64_t ld_out, int64_t chunk_docs, int ld) {
+    int64_t n_arg, const uint8_t* __restrict__ Qb, const uint8_t* __restrict__ Qs, int B, int lq,
+    float* __restrict__ out, int64_t ld_out, int64_t chunk_docs, int ld,
+    const int32_t* __restrict__ ids_arg = nullptr, const int32_t* __restrict__ rag = nullptr) {
   static constexpr int QW = C.qw, AUX = C.aux, WAVES = C.waves, SLOTS = C.slots;
-  static constexpr bool TW2 = C.tw2;
+  static constexpr bool TW2 = C.tw2, IDX = C.idx, RAG = C.rag;
+  static_assert(!RAG || (IDX && QW == 1), "the ragged scan walks one list per query");
   __shared__ __attribute__((aligned(1024))) uint8_t smem[WAVES * SLOTS * kF8SlotBytes];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int c = lane & 15, g = lane >> 4;
   const int nq_groups = (B + QW - 1) / QW;
   const int64_t lin = (int64_t)blockIdx.x * WAVES + wave;      // one doc chunk per wave
-  const int qg = (int)(lin % nq_groups);
-  const int64_t chunk = lin / nq_groups;
+  int qg;
+  int64_t chunk, n = n_arg;
+  const int32_t* ids = ids_arg;
+  if constexpr (RAG) {
+    const int item = (int)lin;                       // (the launcher keeps the chunk total below 2^31)
+    if (item >= sload_len(rag + B)) return;          // surplus wave of the last workgroup
+    int lo = 0, hi = B;                              // the last row whose prefix is <= item: rows without
+    while (hi - lo > 1) {                            // chunks share their successor's prefix and are passed
+      const int mid = (lo + hi) >> 1;
+      if (sload_len(rag + mid) <= item) lo = mid; else hi = mid;
+    }
+    qg = lo;
+    chunk = item - sload_len(rag + lo);
+    n = sload_len(rag + fb_off_count(B) + lo);
+    const uint32_t alo = (uint32_t)sload_len(rag + fb_off_list(B) + 2 * lo);
+    const uint32_t ahi = (uint32_t)sload_len(rag + fb_off_list(B) + 2 * lo + 1);
+    ids = reinterpret_cast<const int32_t*>(((uint64_t)ahi << 32) | alo);
+  } else {
+    qg = (int)(lin % nq_groups);
+    chunk = lin / nq_groups;
+  }
   const int64_t d_begin = chunk * chunk_docs;
   const int64_t d_end = (d_begin + chunk_docs < n) ? d_begin + chunk_docs : n;
   if (d_begin >= d_end) return;  // uniform over the wave; no block-level sync below
   const int nd = (int)(d_end - d_begin);
   uint8_t* ring = smem + wave * (SLOTS * kF8SlotBytes);
-  const int32_t* dls = doclens + d_begin;
+  const int32_t* dls = IDX ? ids + d_begin : doclens + d_begin;   // IDX: the list entries of this range
+  int iid = 0;   // IDX: the doc id of the issue cursor's entry
+  // (32-bit cursor arithmetic, as in maxsim_scan_stream_kernel: every comparison stays on the scalar unit)
   auto ntiles = [&](int d) -> int {
-    int dl = sload_len(dls + d);
+    int dl;
+    if constexpr (IDX) {
+      iid = sload_len(dls + d);
+      dl = sload_len(doclens + iid);
+    } else {
+      dl = sload_len(dls + d);
+    }
     dl = dl < 0 ? 0 : (dl > ld ? ld : dl);
     return (dl + 15) >> 4;
   };
@@ -2613,11 +2669,11 @@ __global__ __launch_bounds__(C.waves * 64, 1) void maxsim_scan_f8_stream_kernel(
   int idoc = 0, itile = 0, intl = ntiles(0);
   while (intl == 0 && ++idoc < nd) intl = ntiles(idoc);
   int issued = 0;
-  const uint8_t* tb = tokens + (size_t)d_begin * ld * kDim;
-  const uint8_t* sb = tscales + (size_t)d_begin * ld * 2;
+  const uint8_t* tb = IDX ? tokens : tokens + (size_t)d_begin * ld * kDim;
+  const uint8_t* sb = IDX ? tscales : tscales + (size_t)d_begin * ld * 2;
   auto issue_next = [&]() {
     if (idoc >= nd) return;
-    const size_t row0 = (size_t)idoc * ld + (size_t)itile * 16;
+    const size_t row0 = (size_t)(IDX ? iid : idoc) * ld + (size_t)itile * 16;
     uint8_t* dst = ring + (issued & (SLOTS - 1)) * kF8SlotBytes;
 #pragma unroll
     for (int p = 0; p < 2; ++p)
@@ -2644,7 +2700,7 @@ __global__ __launch_bounds__(C.waves * 64, 1) void maxsim_scan_f8_stream_kernel(
 
   int consumed = 0;
   for (int i = 0; i < nd; ++i) {
-    int dl = sload_len(dls + i);
+    int dl = IDX ? sload_len(doclens + sload_len(dls + i)) : sload_len(dls + i);
     dl = dl < 0 ? 0 : (dl > ld ? ld : dl);
     const int nt = (dl + 15) >> 4;
     float m[QW][2];
@@ -2987,8 +3043,9 @@ struct FinalMirror {
 };
 constexpr uint64_t kCandWaitTicks = 100000000ull;    // 1 s
 constexpr uint64_t kBackstopTicks = 3000000000ull;   // 30 s: the host committed to publish (gate) yet nothing came
-// Added to a row's band count by a collect workgroup whose wait for phase 1
-// gave up: above any real count (<= k + n < 2^28), so the row overflows.
+// OR-ed into a row's band count by a collect workgroup whose wait for phase 1
+// gave up: a bit above any real count (<= k + n < 2^28), so the row overflows
+// however many workgroups set it.
 constexpr int32_t kWaitTimedOut = 1 << 28;
 // The kernel's side of the wait gate: true = give up (the host had not
 // committed to publish), false = the host is publishing: wait on.
@@ -5375,7 +5432,9 @@ __global__ __launch_bounds__(256, 2) void phase1_collect_kernel(
       __builtin_amdgcn_s_sleep(4);
     }
     s_timed_out = done ? 0 : 1;
-    if (!done) atomicAdd(count + b, kWaitTimedOut);
+    // (OR, not add: a row has up to (n / 64 + 63) / 64 collect workgroups, and 8 to 15 adds of 2^28 wrap the
+    // int32 count negative -- a later workgroup's slot `gp < cap` would then index in front of the band)
+    if (!done) atomicOr(count + b, kWaitTimedOut);
   }
   __syncthreads();
   if (s_timed_out) return;   // block-uniform
@@ -7396,6 +7455,59 @@ int scan_maxsim_subset(cbv2_index* ix, const cbv2_filter* f, const uint16_t* Q, 
   }
 }
 
+// The subset scans of an MXFP8 index (ld = 128): scan_f8's kernels for the
+// same B with the id-list indirection, static split only, compact row out
+// [B][m].  Qb: the quantized queries, their scale bytes behind the B * lq rows.
+constexpr F8StreamCfg with_idx(F8StreamCfg c) { return c.idx = true, c; }
+constexpr F8x4Cfg with_idx(F8x4Cfg c) { return c.idx = true, c; }
+constexpr F8x4Cfg with_d(F8x4Cfg c, int d) { return c.d = d, c; }   // another fold distance
+int launch_f8_stream_ids(cbv2_index* ix, const cbv2_filter* f, const uint8_t* Qb, const uint8_t* Qs, int B, int lq,
+                         float* out, hipStream_t st) {
+  constexpr F8StreamCfg C = with_idx(kF8Stream);
+  const int64_t m = f->m;
+  const int nq_groups = (B + C.qw - 1) / C.qw;
+  const auto [n_chunks, chunk_docs] = chunk_split(m, (int64_t)C.waves * cu_count(ix->device) * kDirectOversub, nq_groups);
+  const int64_t grid = ((int64_t)nq_groups * n_chunks + C.waves - 1) / C.waves;
+  if (grid > 0x7fffffff) return fail(CBV2_EUNSUPPORTED, "scan grid too large");
+  hipLaunchKernelGGL(maxsim_scan_f8_stream_kernel<C>, dim3((unsigned)grid), dim3(C.waves * 64), 0, st, ix->tokens,
+                     ix->scales, ix->doclens, m, Qb, Qs, B, lq, out, m, chunk_docs, (int)ix->ld, f->ids,
+                     (const int32_t*)nullptr);
+  return launch_check("maxsim_scan_f8_stream_kernel (subset)");
+}
+
+template <F8x4Cfg C, int PER_CU>
+int launch_f8x4_ids(cbv2_index* ix, const cbv2_filter* f, const uint8_t* Qb, const uint8_t* Qs, int B, int lq,
+                    float* out, hipStream_t st) {
+  constexpr int QPB = C.waves * C.qw;
+  const int64_t m = f->m;
+  const int nq_groups = (B + QPB - 1) / QPB;
+  const auto [n_chunks, chunk_docs] = chunk_split(m, (int64_t)PER_CU * cu_count(ix->device), nq_groups);
+  if ((int64_t)nq_groups * n_chunks > 0x7fffffff) return fail(CBV2_EUNSUPPORTED, "scan grid too large");
+  hipLaunchKernelGGL(maxsim_scan_f8x4_kernel<with_idx(C)>, dim3((unsigned)(nq_groups * n_chunks)), dim3(C.waves * 64),
+                     0, st, ix->tokens, ix->scales, ix->doclens, m, Qb, Qs, B, lq, out, m, chunk_docs,
+                     /*static_docs=*/m, (int*)nullptr, 0, 0, (uint64_t*)nullptr, 0, 1, (uint64_t*)nullptr, f->ids);
+  return launch_check("maxsim_scan_f8x4_kernel (subset)");
+}
+
+int scan_f8_subset(cbv2_index* ix, const cbv2_filter* f, const uint8_t* Qb, int B, int lq, float* out,
+                   hipStream_t st) {
+  const uint8_t* Qs = Qb + (size_t)B * lq * kDim;
+  if (B <= kF8DirectMaxB) return launch_f8_stream_ids(ix, f, Qb, Qs, B, lq, out, st);   // only the listed docs move
+  switch (pick_shape(kF8Shapes, B)) {   // scan_f8's shape for this B (nt where it streams non-temporally)
+    case kF8ShapeW4Q1: return launch_f8x4_ids<nt(kF8W4Q1), 2>(ix, f, Qb, Qs, B, lq, out, st);
+    case kF8ShapeW4Q2:
+      if (B <= 8) return launch_f8x4_ids<nt(kF8W4Q2), 2>(ix, f, Qb, Qs, B, lq, out, st);
+      return launch_f8x4_ids<kF8W4Q2, 2>(ix, f, Qb, Qs, B, lq, out, st);
+    case kF8ShapeW4Q4:
+      if (B <= 16) return launch_f8x4_ids<nt(kF8W4Q4), 3>(ix, f, Qb, Qs, B, lq, out, st);
+      return launch_f8x4_ids<kF8W4Q4, 3>(ix, f, Qb, Qs, B, lq, out, st);
+    case kF8ShapeW4Q8: return launch_f8x4_ids<kF8W4Q8, 2>(ix, f, Qb, Qs, B, lq, out, st);
+    // 8 x 8 (PAIR ring): fold distance 1 -- with the indirection, distance 3 spills 2 VGPRs (12 B of scratch per
+    // lane; profiles/filter_fp8_resource_usage.md); the max is exact, so the bits do not depend on the distance
+    default: return launch_f8x4_ids<with_d(kF8W8Q8, 1), 1>(ix, f, Qb, Qs, B, lq, out, st);
+  }
+}
+
 // The faithful subset: cbv2_score_f32's arithmetic (one (query, doc) pair per
 // workgroup, all three products in the kernel) over the id list -- the same
 // list for every row (ld_c = 0), local ids (id_base 0).  only_neg (nullable):
@@ -7415,7 +7527,7 @@ int rescore_subset(cbv2_index* ix, const cbv2_filter* f, const F32Ws* w, int B, 
 }
 
 // Path and workspace layout of a filtered search.  The subset path: MaxSim on
-// a bf16 (or fp32-faithful) index of 128-slot docs; everything else -- and
+// a bf16 (or fp32-faithful) or MXFP8 index of 128-slot docs; everything else -- and
 // CBV2_OPT_FILTER_PATH = 2 -- scores every doc and gathers the allowed columns.
 // CBV2_OPT_FILTER_PATH = 0 takes the subset path when it is supported and
 // m <= kFilterSubsetMaxFrac * n: the largest density of the sweep at which the
@@ -7425,10 +7537,20 @@ int rescore_subset(cbv2_index* ix, const cbv2_filter* f, const F32Ws* w, int B, 
 // and 152.2 vs 149.9; faithful B=1 5.19 vs 10.41 and 10.60 vs 10.42 -- the
 // list's indirection costs ~5 % of a full scan).
 constexpr double kFilterSubsetMaxFrac = 0.5;
+// An MXFP8 index (ld = 128, MaxSim) has the subset path too (scan_f8_subset),
+// with a density of its own by the same rule (tools/filter_sweep.py --kinds
+// mxfp8, 1M docs, medians of 5, profiles/filter_sweep_mxfp8.jsonl; subset vs
+// dense): B=1 1.31 vs 2.44 ms at 0.5 and 2.52 vs 2.43 at 1.0; B=16 3.18 vs
+// 5.60 and 6.34 vs 5.69; B=256 38.4 vs 73.4 and 76.7 vs 74.4 -- the
+// indirection (and, at B > 32, the 8 x 8 shape's fold distance 1) costs 3-11 %
+// of a full scan; at 0.001 B=1 0.056 vs 2.43 ms.
+constexpr double kFilterSubsetMaxFracF8 = 0.5;
 bool filter_takes_subset(const cbv2_index* ix, int64_t m_allowed, int32_t scorer) {
-  const bool supported = scorer == CBV2_SCORER_MAXSIM && ix->dtype == CBV2_DTYPE_BF16 && ix->ld == kLd;
-  return supported && (ix->filter_path == 1 ||
-                       (ix->filter_path == 0 && (double)m_allowed <= kFilterSubsetMaxFrac * (double)ix->n));
+  const bool f8 = ix->dtype == CBV2_DTYPE_MXFP8;
+  const bool supported = scorer == CBV2_SCORER_MAXSIM && (ix->dtype == CBV2_DTYPE_BF16 || f8) && ix->ld == kLd;
+  const double frac = f8 ? kFilterSubsetMaxFracF8 : kFilterSubsetMaxFrac;
+  return supported &&
+         (ix->filter_path == 1 || (ix->filter_path == 0 && (double)m_allowed <= frac * (double)ix->n));
 }
 
 // ---------------------------------------------------------------------------
@@ -7697,6 +7819,19 @@ int launch_stream_ragged(cbv2_index* ix, const cbv2_filter_batch* fb, const uint
                      (int64_t)0, Q, B, lq, out, M, fb->chunk_docs, (int)ix->ld, (uint32_t*)nullptr, (int64_t)0,
                      (uint32_t*)nullptr, (int64_t)0, (const int32_t*)nullptr, fb->table);
   return launch_check("maxsim_scan_stream_kernel (ragged)");
+}
+
+// The same for an MXFP8 index: the f8 streaming scan's 8-wave workgroups,
+// ceil(chunks / 8) of them (cbv2_filter_batch_create sized the chunks for them).
+int launch_f8_stream_ragged(cbv2_index* ix, const cbv2_filter_batch* fb, const uint8_t* Qb, int B, int lq, float* out,
+                            int64_t M, hipStream_t st) {
+  constexpr F8StreamCfg C{.qw = 1, .aux = 2, .waves = kF8Stream.waves, .slots = kF8Stream.slots, .idx = true, .rag = true};
+  const int64_t grid = (fb->chunks + C.waves - 1) / C.waves;
+  if (grid < 1 || grid > 0x0fffffff) return fail(CBV2_EUNSUPPORTED, "scan grid too large");
+  hipLaunchKernelGGL(maxsim_scan_f8_stream_kernel<C>, dim3((unsigned)grid), dim3(C.waves * 64), 0, st, ix->tokens,
+                     ix->scales, ix->doclens, (int64_t)0, Qb, Qb + (size_t)B * lq * kDim, B, lq, out, M,
+                     fb->chunk_docs, (int)ix->ld, (const int32_t*)nullptr, fb->table);
+  return launch_check("maxsim_scan_f8_stream_kernel (ragged)");
 }
 
 // The faithful rows: rescore_subset's launch over the per-row candidate matrix
@@ -8135,7 +8270,9 @@ int cbv2_search_filtered(cbv2_index* ix, const cbv2_filter* f, int32_t scorer, c
   float* dense = (float*)((uint8_t*)ws + p.off_dense);
   int rc;
   if (p.subset) {
-    if ((rc = scan_maxsim_subset(ix, f, (const uint16_t*)Q, B, lq, row, st))) return rc;
+    rc = ix->dtype == CBV2_DTYPE_MXFP8 ? scan_f8_subset(ix, f, (const uint8_t*)Q, B, lq, row, st)
+                                       : scan_maxsim_subset(ix, f, (const uint16_t*)Q, B, lq, row, st);
+    if (rc) return rc;
   } else {
     if ((rc = score_impl(ix, scorer, Q, B, lq, dense, ix->n, st, ctr))) return rc;
     const int64_t gx = std::min<int64_t>((m + 255) / 256, 4096);
@@ -8182,9 +8319,11 @@ int cbv2_filter_batch_create(const cbv2_index* ix, const cbv2_filter* const* per
   if (!dg.ok) return fail(CBV2_EHIP, "cannot select device %d", ix->device);
   // docs per work item: as launch_stream_ids sizes its chunks -- the chip's
   // resident waves times the oversubscription, here over all rows' pairs
+  // (an MXFP8 index: launch_f8_stream_ids' 8 waves per CU)
   int64_t chunk_docs = ix->filter_batch_chunk_docs;
   if (chunk_docs <= 0) {
-    const int64_t target_waves = 4LL * cu_count(ix->device) * kDirectOversub;
+    const int64_t waves_per_cu = ix->dtype == CBV2_DTYPE_MXFP8 ? kF8Stream.waves : 4;
+    const int64_t target_waves = waves_per_cu * cu_count(ix->device) * kDirectOversub;
     chunk_docs = std::max<int64_t>(1, (pairs + target_waves - 1) / target_waves);
   }
   std::vector<int32_t> tab((size_t)fb_table_ints(B));
@@ -8276,8 +8415,9 @@ int cbv2_search_filtered_batch(cbv2_index* ix, const cbv2_filter_batch* fb, int3
     hipLaunchKernelGGL(fb_prepare_kernel, dim3(gx, gy), dim3(256), 0, st, fb->table, B, M,
                        faithful ? cand : (int32_t*)nullptr, row);
     if ((rc = launch_check("fb_prepare_kernel"))) return rc;
-    rc = faithful ? rescore_ragged(ix, fb, &w, B, lq, cand, row, M, st)
-                  : launch_stream_ragged(ix, fb, (const uint16_t*)Q, B, lq, row, M, st);
+    rc = faithful                         ? rescore_ragged(ix, fb, &w, B, lq, cand, row, M, st)
+         : ix->dtype == CBV2_DTYPE_MXFP8 ? launch_f8_stream_ragged(ix, fb, (const uint8_t*)Q, B, lq, row, M, st)
+                                         : launch_stream_ragged(ix, fb, (const uint16_t*)Q, B, lq, row, M, st);
     if (rc) return rc;
   } else {
     rc = faithful ? launch_rescore(ix, &w, B, lq, nullptr, nullptr, ix->n, 0, dense, ix->n, st)

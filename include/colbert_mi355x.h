@@ -231,7 +231,8 @@ int cbv2_index_scan_clock(cbv2_index* index, int64_t* out4, int32_t reset);
  *  CBV2_OPT_FILTER_PATH   cbv2_search_filtered's path: 0 automatic (the subset
  *                        path where it is supported and m <= 0.5 n, the
  *                        largest measured density at which it still beat the
- *                        dense path: DESIGN.md 3.8), 1 the subset path where
+ *                        dense path, for bf16, fp32-faithful and MXFP8
+ *                        indexes alike: DESIGN.md 3.8), 1 the subset path where
  *                        supported, 2 the dense path (score every doc, gather
  *                        the allowed columns).  Identical results.
  *  CBV2_OPT_FILTER_BAND   the filtered faithful search (cbv2_search_filtered_f32,
@@ -354,13 +355,15 @@ int cbv2_search(cbv2_index* index, int32_t scorer, const void* Q, int32_t q_dtyp
  *    cbv2_search_filtered_workspace_size(index, filter, B, lq, k, scorer)
  *    bytes, computed with the options the search will run under.
  *    Two paths, same results (CBV2_OPT_FILTER_PATH):
- *    subset -- MaxSim on a bf16 or fp32-faithful index of 128-slot docs: the
- *      scan walks the id list (doc lengths and base addresses through it) and
+ *    subset -- MaxSim on a bf16, fp32-faithful or MXFP8 index of 128-slot
+ *      docs: the scan walks the id list (doc lengths and base addresses -- on
+ *      an MXFP8 index the token and the scale rows -- through it) and
  *      writes a compact row [B][m] -- B <= 2 the streaming scan, moving only
  *      the listed docs' token tiles; larger B the doc-interleaved MFMA scans,
  *      each listed doc loaded once per query group; faithful: one faithful
  *      score (lo.qhi + hi.qlo + hi.qhi in one kernel) per (query, allowed doc);
- *    dense -- everything else (MXFP8, long documents, REF_MEANPOOL_COSINE):
+ *      no [B][n] block in the workspace;
+ *    dense -- everything else (long documents, REF_MEANPOOL_COSINE):
  *      the full scorer into [B][n], then a gather of the allowed columns.
  *    Both end in the row top-k and a map of row positions to
  *    id_base + ids[pos] (the list is ascending: position order is id order). */
@@ -453,6 +456,8 @@ cbv2_search_filtered_f32(cbv2_index* index, const cbv2_filter* filter, const flo
  *      wave's work item is (row b, chunk of row b's list), found by a search
  *      of the table's prefix; each (query, allowed doc) pair is streamed and
  *      scored on its own (queries sharing a filter share no loads);
+ *    subset, MXFP8 -- the same ragged scan on e4m3 tiles (the MXFP8 streaming
+ *      scan's 8-wave workgroups; token and scale rows through the lists);
  *    subset, faithful -- the lists gathered into a candidate matrix [B][M],
  *      then one faithful score per (query, allowed doc), count[b] = m_b;
  *    dense -- the full scorer into [B][n], then a ragged gather.

@@ -1,11 +1,12 @@
 #!/usr/bin/env python3
 """Filtered-search sweep: the unfiltered search (the yardstick) against the
 subset and the dense path of cbv2_search_filtered over filter densities, on one
-synthetic index per kind (bf16, fp32-faithful), one GPU.
+synthetic index per kind (bf16, fp32-faithful, mxfp8), one GPU.
 
     python tools/filter_sweep.py [--docs 1000000] [--kinds bf16,faithful] [--batches 1,16,256]
                                  [--densities 0.001,0.01,0.1,0.25,0.5,1.0] [--reps 5]
                                  [--out profiles/filter_sweep.jsonl]
+    python tools/filter_sweep.py --kinds mxfp8      (-> profiles/filter_sweep_mxfp8.jsonl)
 
 One child process per index kind, each under its own time limit (--limit
 seconds); a child that fails or runs out of time stops the chain.  Inside a
@@ -18,8 +19,11 @@ B = 256 over 1M docs is 2.6e8 of them).
 
 Per point: ms of the three, the subset path's allowed bytes / FLOP and the
 rate it reached over them (B = 1: share of the 8 TB/s HBM peak; B = 256: share
-of the 2.5 PFLOP/s bf16 MFMA peak), and whether subset and dense returned the
-same bits.  f of a kind = the largest measured density at which the subset
+of the 2.5 PFLOP/s bf16 MFMA peak; mxfp8: of the 5 PFLOP/s fp8 dense peak,
+bytes per doc 128 * 128 + 256), the same two rates of the unfiltered scan over
+the whole shard, and whether subset and dense returned the same bits (an mxfp8
+child stops at a point where they differ).  The mxfp8 index is
+ColbertIndex.mxfp8 and every leg quantizes its bf16 queries inside the call.  f of a kind = the largest measured density at which the subset
 path is still faster than the dense path at every measured B.
 """
 import argparse
@@ -31,7 +35,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-PEAK_HBM_GBS, PEAK_BF16_TFLOPS = 8000.0, 2500.0
+PEAK_HBM_GBS, PEAK_BF16_TFLOPS, PEAK_FP8_TFLOPS = 8000.0, 2500.0, 5000.0
 
 
 def child(a):
@@ -54,7 +58,12 @@ def child(a):
         Qall = Qf.to(dev)
     else:
         tok, dl = synth.make_shard(0, a.docs, Qf, planted, dev, seed=0)
-        ix = ColbertIndex(tok, dl)
+        if a.kind == "mxfp8":
+            ix = ColbertIndex.mxfp8(tok, dl)
+            del tok
+            torch.cuda.empty_cache()
+        else:
+            ix = ColbertIndex(tok, dl)
         Qall = Qf.to(dev, torch.bfloat16)
     rng = np.random.default_rng(5)
     out = open(a.out, "a")
@@ -98,18 +107,27 @@ def child(a):
                 rec["identical"] = bool(torch.equal(res["subset"][0], res["dense"][0])
                                         and torch.equal(res["subset"][1], res["dense"][1]))
             if "subset" in ts:
-                per_doc = 128 * 128 * 2 * (2 if a.kind == "faithful" else 1)        # hi (+ lo) bytes of a doc
+                # bytes of a doc: hi (+ lo) bf16 tokens; mxfp8: e4m3 tokens + 2 scale bytes per token
+                per_doc = 128 * 128 + 256 if a.kind == "mxfp8" else 128 * 128 * 2 * (2 if a.kind == "faithful" else 1)
                 flop = 2.0 * B * 32 * m * 128 * 128 * (3 if a.kind == "faithful" else 1)
+                peak = PEAK_FP8_TFLOPS if a.kind == "mxfp8" else PEAK_BF16_TFLOPS
                 sec = rec["ms"]["subset"] * 1e-3
                 rec["subset_allowed_gb"] = round(m * per_doc / 1e9, 4)
                 rec["subset_gbs_over_allowed_bytes"] = round(m * per_doc / 1e9 / sec, 1)
                 rec["subset_hbm_share"] = round(m * per_doc / 1e9 / sec / PEAK_HBM_GBS, 4)
                 rec["subset_tflops_over_allowed_flop"] = round(flop / 1e12 / sec, 2)
-                rec["subset_mfma_share"] = round(flop / 1e12 / sec / PEAK_BF16_TFLOPS, 4)
+                rec["subset_mfma_share"] = round(flop / 1e12 / sec / peak, 4)
+                if a.kind == "mxfp8":       # the unfiltered search of the same run, over the whole shard
+                    usec = rec["ms"]["unfiltered"] * 1e-3
+                    rec["unfiltered_gbs"] = round(a.docs * per_doc / 1e9 / usec, 1)
+                    rec["unfiltered_tflops"] = round(flop * a.docs / m / 1e12 / usec, 2)
+                    rec["unfiltered_mfma_share"] = round(flop * a.docs / m / 1e12 / usec / peak, 4)
             line = json.dumps(rec)
             print(line, flush=True)
             out.write(line + "\n")
             out.flush()
+            if a.kind == "mxfp8" and not rec.get("identical", True):
+                sys.exit(f"[filter_sweep] mxfp8 B={B} density={s}: subset and dense differ")
         flt.close()
     ix.set_option(_lib.OPT_FILTER_PATH, _lib.FILTER_AUTO)
 
@@ -123,9 +141,11 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--pair-cap", type=int, default=20_000_000)
     ap.add_argument("--limit", type=int, default=540, help="seconds per index kind (one child process each)")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "filter_sweep.jsonl"))
+    ap.add_argument("--out", default=None, help="profiles/filter_sweep.jsonl (--kinds mxfp8: filter_sweep_mxfp8.jsonl)")
     ap.add_argument("--kind", default=None, help=argparse.SUPPRESS)     # set for the child
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "filter_sweep_mxfp8.jsonl" if a.kinds == "mxfp8" else "filter_sweep.jsonl")
     if a.kind is not None:
         return child(a)
     os.makedirs(os.path.dirname(a.out), exist_ok=True)

@@ -29,7 +29,8 @@ def main():
     cur = None
     rows = []
     for line in out.splitlines():
-        m = re.search(r"remark:\s+(Function Name|VGPRs|AGPRs|VGPRs Spill|SGPRs Spill|LDS Size \[bytes/block\]|"
+        m = re.search(r"remark:\s+(Function Name|VGPRs|AGPRs|VGPRs Spill|SGPRs Spill|ScratchSize \[bytes/lane\]|"
+                      r"LDS Size \[bytes/block\]|"
                       r"Occupancy \[waves/SIMD\]): (\S+)", line)
         if not m:
             continue
@@ -46,7 +47,8 @@ def main():
                               text=True).stdout.strip()
         name = name.replace("(anonymous namespace)::", "")
         print(f"vgpr {r.get('VGPRs', '?'):>4} agpr {r.get('AGPRs', '?'):>3} vspill {r.get('VGPRs Spill', '?'):>3} "
-              f"sspill {r.get('SGPRs Spill', '?'):>3} lds {r.get('LDS Size [bytes/block]', '?'):>6} "
+              f"sspill {r.get('SGPRs Spill', '?'):>3} scratch {r.get('ScratchSize [bytes/lane]', '?'):>3} "
+              f"lds {r.get('LDS Size [bytes/block]', '?'):>6} "
               f"occ {r.get('Occupancy [waves/SIMD]', '?')}  {name[:150]}")
     return 0
 
