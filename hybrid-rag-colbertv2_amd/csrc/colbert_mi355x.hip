@@ -1392,11 +1392,15 @@ __global__ __launch_bounds__(C.waves * 64, C.occ) void maxsim_scan16x4_kernel(
 // LONG: docs of ld = 256 / 512 / 1024 token slots, scored 128 tokens at a time
 // with the row maxima carried across the blocks (same tile order: the bits of
 // a doc of <= 128 tokens do not depend on ld).
-template <int QW, bool LONG = false>
+// IDX (the filtered search's subset scan, as maxsim_scan_stream_kernel's): the
+// n "docs" are the entries of an ascending list of local doc ids -- entry i is
+// doc ids[i], whose length and base address go through the list, and its score
+// lands in column i of the compact row.
+template <int QW, bool LONG = false, bool IDX = false>
 __global__ __launch_bounds__(256, 2) void maxsim_scan_direct_kernel(
     const uint8_t* __restrict__ tokens, const int32_t* __restrict__ doclens, int64_t n,
     const uint16_t* __restrict__ Q, int B, int lq, float* __restrict__ out, int64_t ld_out,
-    int64_t chunk_docs, int ld = kLd) {
+    int64_t chunk_docs, int ld = kLd, const int32_t* __restrict__ ids = nullptr) {
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int g = lane >> 4;
@@ -1418,14 +1422,15 @@ __global__ __launch_bounds__(256, 2) void maxsim_scan_direct_kernel(
 
   for (int i = 0; i < nd; ++i) {
     const int lmax = LONG ? ld : kLd;
-    int dl = doclens[d_begin + i];
+    const int64_t di = IDX ? (int64_t)ids[d_begin + i] : d_begin + i;   // wave-uniform
+    int dl = doclens[di];
     dl = dl < 0 ? 0 : (dl > lmax ? lmax : dl);
     float m[QW][2];
 #pragma unroll
     for (int q = 0; q < QW; ++q) m[q][0] = m[q][1] = neg_inf();
     for (int blk = 0; blk == 0 || (LONG && kLd * blk < dl); ++blk) {   // one block unless LONG
       const int dlb = dl - kLd * blk;
-      const uint8_t* dbase = tokens + (size_t)(d_begin + i) * (size_t)lmax * kRowBytes + (size_t)blk * kDocBytes;
+      const uint8_t* dbase = tokens + (size_t)di * (size_t)lmax * kRowBytes + (size_t)blk * kDocBytes;
       bf16x8 af[kLd / 16][4];
 #pragma unroll
       for (int rt = 0; rt < kLd / 16; ++rt)
@@ -7411,8 +7416,9 @@ size_t filter_buf_layout(int64_t n, size_t* off_blk, size_t* off_off, size_t* of
   return off + 256;
 }
 
-// The subset scans of a bf16 index (ld = 128): the production kernels with the
-// id-list indirection (IDX), static split only, compact row out [B][m].
+// The subset scans of a bf16 index: the production kernels with the id-list
+// indirection (IDX), static split only, compact row out [B][m].  ld = 128: the
+// shapes of scan_maxsim; long documents: those of scan_maxsim_long.
 template <int QW>
 int launch_stream_ids(cbv2_index* ix, const cbv2_filter* f, const uint16_t* Q, int B, int lq, float* out,
                       hipStream_t st) {
@@ -7443,8 +7449,39 @@ int launch_scan16x4_ids(cbv2_index* ix, const cbv2_filter* f, const uint16_t* Q,
   return launch_check("maxsim_scan16x4_kernel (subset)");
 }
 
+// Long documents, B = 3 .. kLongDirectMaxB: launch_direct's kernel and split over the list.
+int launch_direct_ids(cbv2_index* ix, const cbv2_filter* f, const uint16_t* Q, int B, int lq, float* out,
+                      hipStream_t st) {
+  constexpr int QW = 2;
+  const int64_t m = f->m;
+  const int nq_groups = (B + QW - 1) / QW;
+  const auto [n_chunks, chunk_docs] = chunk_split(m, 8LL * cu_count(ix->device) * kDirectOversub, nq_groups);
+  const int64_t grid = ((int64_t)nq_groups * n_chunks + 3) / 4;
+  if (grid > 0x7fffffff) return fail(CBV2_EUNSUPPORTED, "scan grid too large");
+  hipLaunchKernelGGL((maxsim_scan_direct_kernel<QW, true, true>), dim3((unsigned)grid), dim3(256), 0, st, ix->tokens,
+                     ix->doclens, m, Q, B, lq, out, m, chunk_docs, (int)ix->ld, f->ids);
+  return launch_check("maxsim_scan_direct_kernel (subset)");
+}
+
+// ... and scan_maxsim_long's dispatch over the list: a given B runs the same
+// shape filtered and unfiltered (the streaming scan takes ld at run time).
+int scan_maxsim_subset_long(cbv2_index* ix, const cbv2_filter* f, const uint16_t* Q, int B, int lq, float* out,
+                            hipStream_t st) {
+  if (B <= kDirectMaxB)
+    return B == 1 ? launch_stream_ids<1>(ix, f, Q, B, lq, out, st) : launch_stream_ids<2>(ix, f, Q, B, lq, out, st);
+  if (B <= kLongDirectMaxB) return launch_direct_ids(ix, f, Q, B, lq, out, st);
+  switch (ix->ld) {
+    case 256: return launch_scan16x4_ids<with_ld(kW8, 256), 1>(ix, f, Q, B, lq, out, st);
+    case 512: return launch_scan16x4_ids<with_ld(kW8, 512), 1>(ix, f, Q, B, lq, out, st);
+    case 1024: return launch_scan16x4_ids<with_ld(kW8, 1024), 1>(ix, f, Q, B, lq, out, st);
+    default:
+      return fail(CBV2_EUNSUPPORTED, "index ld %d not built", (int)ix->ld);
+  }
+}
+
 int scan_maxsim_subset(cbv2_index* ix, const cbv2_filter* f, const uint16_t* Q, int B, int lq, float* out,
                        hipStream_t st) {
+  if (ix->ld != kLd) return scan_maxsim_subset_long(ix, f, Q, B, lq, out, st);
   if (B <= kDirectMaxB)   // HBM-bound: only the listed docs' token tiles move
     return B == 1 ? launch_stream_ids<1>(ix, f, Q, B, lq, out, st) : launch_stream_ids<2>(ix, f, Q, B, lq, out, st);
   switch (pick_shape(kBf16Shapes, B)) {   // each listed doc is loaded once per query group
@@ -7455,8 +7492,8 @@ int scan_maxsim_subset(cbv2_index* ix, const cbv2_filter* f, const uint16_t* Q, 
   }
 }
 
-// The subset scans of an MXFP8 index (ld = 128): scan_f8's kernels for the
-// same B with the id-list indirection, static split only, compact row out
+// The subset scans of an MXFP8 index: scan_f8's (long documents: scan_f8_long's)
+// kernels for the same B with the id-list indirection, static split only, compact row out
 // [B][m].  Qb: the quantized queries, their scale bytes behind the B * lq rows.
 constexpr F8StreamCfg with_idx(F8StreamCfg c) { return c.idx = true, c; }
 constexpr F8x4Cfg with_idx(F8x4Cfg c) { return c.idx = true, c; }
@@ -7489,10 +7526,28 @@ int launch_f8x4_ids(cbv2_index* ix, const cbv2_filter* f, const uint8_t* Qb, con
   return launch_check("maxsim_scan_f8x4_kernel (subset)");
 }
 
+// Long documents: launch_f8_long's two shapes over the list.
+template <int LD>
+int launch_f8_long_ids(cbv2_index* ix, const cbv2_filter* f, const uint8_t* Qb, const uint8_t* Qs, int B, int lq,
+                       float* out, hipStream_t st) {
+  if (B <= kF8SmallMaxB) return launch_f8x4_ids<with_ld(kF8W4Q2, LD), 2>(ix, f, Qb, Qs, B, lq, out, st);
+  // 8 x 8 (3-deep ring): fold distance 1 -- with the indirection, distance 3 spills 2 VGPRs at every LD (12 B of
+  // scratch per lane; profiles/filter_long_resource_usage.md), as the 128-slot launch below; the max is exact
+  return launch_f8x4_ids<with_d(with_ld(kF8W8Q8Ring3, LD), 1), 1>(ix, f, Qb, Qs, B, lq, out, st);
+}
+
 int scan_f8_subset(cbv2_index* ix, const cbv2_filter* f, const uint8_t* Qb, int B, int lq, float* out,
                    hipStream_t st) {
   const uint8_t* Qs = Qb + (size_t)B * lq * kDim;
   if (B <= kF8DirectMaxB) return launch_f8_stream_ids(ix, f, Qb, Qs, B, lq, out, st);   // only the listed docs move
+  switch (ix->ld) {   // long documents: scan_f8_long's shapes
+    case kLd: break;
+    case 256: return launch_f8_long_ids<256>(ix, f, Qb, Qs, B, lq, out, st);
+    case 512: return launch_f8_long_ids<512>(ix, f, Qb, Qs, B, lq, out, st);
+    case 1024: return launch_f8_long_ids<1024>(ix, f, Qb, Qs, B, lq, out, st);
+    default:
+      return fail(CBV2_EUNSUPPORTED, "index ld %d not built", (int)ix->ld);
+  }
   switch (pick_shape(kF8Shapes, B)) {   // scan_f8's shape for this B (nt where it streams non-temporally)
     case kF8ShapeW4Q1: return launch_f8x4_ids<nt(kF8W4Q1), 2>(ix, f, Qb, Qs, B, lq, out, st);
     case kF8ShapeW4Q2:
@@ -7518,7 +7573,8 @@ int rescore_subset(cbv2_index* ix, const cbv2_filter* f, const F32Ws* w, int B, 
                    const int32_t* only_neg = nullptr) {
   const int64_t span = only_neg != nullptr ? std::min<int64_t>(f->m, std::max<int64_t>(64, 256 / B)) : f->m;
   const auto [gx, two] = rescore_grid(ix, B, span);   // a row's pairs beyond the grid stride it
-  auto kern = two ? rescore_split_kernel<false, 2> : rescore_split_kernel<false, 4>;
+  auto kern = ix->ld != kLd ? rescore_split_kernel<true, 4>   // (long documents: never two, as launch_rescore)
+                            : (two ? rescore_split_kernel<false, 2> : rescore_split_kernel<false, 4>);
   hipLaunchKernelGGL(kern, dim3(gx, (unsigned)B), dim3(two ? 128 : 256), 0, st, ix->tokens, ix->resid, ix->doclens,
                      ix->n, (int64_t)0, w->qhi, w->qlo, lq, f->ids, (const int32_t*)nullptr, f->m, (int64_t)0, out,
                      f->m, only_neg, (int)ix->ld, (uint32_t*)nullptr, (int64_t)0, (float*)nullptr,
@@ -7527,7 +7583,7 @@ int rescore_subset(cbv2_index* ix, const cbv2_filter* f, const F32Ws* w, int B, 
 }
 
 // Path and workspace layout of a filtered search.  The subset path: MaxSim on
-// a bf16 (or fp32-faithful) or MXFP8 index of 128-slot docs; everything else -- and
+// a bf16 (or fp32-faithful) or MXFP8 index, long documents included; everything else -- and
 // CBV2_OPT_FILTER_PATH = 2 -- scores every doc and gathers the allowed columns.
 // CBV2_OPT_FILTER_PATH = 0 takes the subset path when it is supported and
 // m <= kFilterSubsetMaxFrac * n: the largest density of the sweep at which the
@@ -7545,10 +7601,27 @@ constexpr double kFilterSubsetMaxFrac = 0.5;
 // indirection (and, at B > 32, the 8 x 8 shape's fold distance 1) costs 3-11 %
 // of a full scan; at 0.001 B=1 0.056 vs 2.43 ms.
 constexpr double kFilterSubsetMaxFracF8 = 0.5;
+// Long documents (ld = 256 / 512 / 1024) have the subset path for both index
+// dtypes (scan_maxsim_subset_long, launch_f8_long_ids, the LONG pair kernel),
+// with densities of their own by the same rule (tools/filter_sweep.py --ld 512:
+// 250,000 full docs, the 1M-doc sweep's bytes, medians of 5, profiles/
+// filter_sweep_long.jsonl; ld = 256 and 1024 at the same bytes gave the same f:
+// filter_sweep_long_ld256.jsonl, _ld1024.jsonl; subset vs dense at 512): bf16 B=1
+// 2.39 vs 4.71 ms at 0.5 and 4.73 vs 4.72 at 1.0; B=16 8.97 vs 17.35 and 17.53
+// vs 17.44; B=256 73.1 vs 142.1 and 146.7 vs 142.4; faithful B=1 2.48 vs 10.09
+// and 4.79 vs 10.10 (it wins at every measured point, but shares the bf16
+// index's constant); at 0.001 B=1 bf16 0.046 vs 4.66 ms, faithful 0.072 vs 10.24.
+constexpr double kFilterSubsetMaxFracLong = 0.5;
+// MXFP8: B=1 1.30 vs 2.47 ms at 0.5 and 2.48 vs 2.47 at 1.0; B=16 8.38 vs 15.73
+// and 16.68 vs 15.92; B=256 38.4 vs 72.3 and 76.6 vs 73.2 (the 8 x 8 shape's
+// fold distance 1 and the indirection: 5 % of a full scan); at 0.001 B=1 0.063
+// vs 2.49 ms.
+constexpr double kFilterSubsetMaxFracLongF8 = 0.5;
 bool filter_takes_subset(const cbv2_index* ix, int64_t m_allowed, int32_t scorer) {
   const bool f8 = ix->dtype == CBV2_DTYPE_MXFP8;
-  const bool supported = scorer == CBV2_SCORER_MAXSIM && (ix->dtype == CBV2_DTYPE_BF16 || f8) && ix->ld == kLd;
-  const double frac = f8 ? kFilterSubsetMaxFracF8 : kFilterSubsetMaxFrac;
+  const bool supported = scorer == CBV2_SCORER_MAXSIM && (ix->dtype == CBV2_DTYPE_BF16 || f8);
+  const double frac = ix->ld != kLd ? (f8 ? kFilterSubsetMaxFracLongF8 : kFilterSubsetMaxFracLong)
+                                    : (f8 ? kFilterSubsetMaxFracF8 : kFilterSubsetMaxFrac);
   return supported &&
          (ix->filter_path == 1 || (ix->filter_path == 0 && (double)m_allowed <= frac * (double)ix->n));
 }
@@ -7592,7 +7665,10 @@ bool filter_takes_subset(const cbv2_index* ix, int64_t m_allowed, int32_t scorer
 //   (256,000: 4.9 vs 6.3 ms) and at every larger point.
 // The two constants put the threshold between the last point the pair path won
 // and the first the band won at both k (k = 100: 2,800 .. 9,800; k = 1,000:
-// 16,000 .. 28,000); no other k was measured.
+// 16,000 .. 28,000); no other k was measured.  Long documents keep the two
+// constants, unmeasured there: a pair and a scanned doc both cost ld / 128 times
+// more while the band's extra launches cost the same, so the rule switches to
+// the band later than it could.
 // ---------------------------------------------------------------------------
 constexpr int64_t kFilterBandMinSavedPairs = 4000;
 constexpr int64_t kFilterBandSavedPairsPerK = 16;
@@ -7839,7 +7915,8 @@ int launch_f8_stream_ragged(cbv2_index* ix, const cbv2_filter_batch* fb, const u
 int rescore_ragged(cbv2_index* ix, const cbv2_filter_batch* fb, const F32Ws* w, int B, int lq, const int32_t* cand,
                    float* out, int64_t M, hipStream_t st) {
   const auto [gx, two] = rescore_grid(ix, B, M);   // a row's pairs beyond the grid stride it
-  auto kern = two ? rescore_split_kernel<false, 2> : rescore_split_kernel<false, 4>;
+  auto kern = ix->ld != kLd ? rescore_split_kernel<true, 4>   // (long documents: never two, as launch_rescore)
+                            : (two ? rescore_split_kernel<false, 2> : rescore_split_kernel<false, 4>);
   hipLaunchKernelGGL(kern, dim3(gx, (unsigned)B), dim3(two ? 128 : 256), 0, st, ix->tokens, ix->resid, ix->doclens,
                      ix->n, (int64_t)0, w->qhi, w->qlo, lq, cand, fb->table + fb_off_count(B), M, M, out, M,
                      (const int32_t*)nullptr, (int)ix->ld, (uint32_t*)nullptr, (int64_t)0, (float*)nullptr,

@@ -232,9 +232,13 @@ int cbv2_index_scan_clock(cbv2_index* index, int64_t* out4, int32_t reset);
  *                        path where it is supported and m <= 0.5 n, the
  *                        largest measured density at which it still beat the
  *                        dense path, for bf16, fp32-faithful and MXFP8
- *                        indexes alike: DESIGN.md 3.8), 1 the subset path where
- *                        supported, 2 the dense path (score every doc, gather
- *                        the allowed columns).  Identical results.
+ *                        indexes alike, of 128-slot docs (measured at 1M
+ *                        docs) and of long documents (measured at ld = 256,
+ *                        512 and 1024, 32 GB of bf16 tokens each): DESIGN.md
+ *                        3.8), 1 the subset path where
+ *                        supported (MaxSim, every index kind and ld), 2 the
+ *                        dense path (score every doc, gather the allowed
+ *                        columns).  Identical results.
  *  CBV2_OPT_FILTER_BAND   the filtered faithful search (cbv2_search_filtered_f32,
  *                        cbv2_search_filtered with f32 queries) where
  *                        CBV2_OPT_FILTER_PATH resolves to the subset path: 0
@@ -355,15 +359,16 @@ int cbv2_search(cbv2_index* index, int32_t scorer, const void* Q, int32_t q_dtyp
  *    cbv2_search_filtered_workspace_size(index, filter, B, lq, k, scorer)
  *    bytes, computed with the options the search will run under.
  *    Two paths, same results (CBV2_OPT_FILTER_PATH):
- *    subset -- MaxSim on a bf16, fp32-faithful or MXFP8 index of 128-slot
- *      docs: the scan walks the id list (doc lengths and base addresses -- on
+ *    subset -- MaxSim on a bf16, fp32-faithful or MXFP8 index, of 128-slot
+ *      docs or long documents (ld = 256 / 512 / 1024: the unfiltered long-doc
+ *      scan's shape for the same B): the scan walks the id list (doc lengths and base addresses -- on
  *      an MXFP8 index the token and the scale rows -- through it) and
  *      writes a compact row [B][m] -- B <= 2 the streaming scan, moving only
  *      the listed docs' token tiles; larger B the doc-interleaved MFMA scans,
  *      each listed doc loaded once per query group; faithful: one faithful
  *      score (lo.qhi + hi.qlo + hi.qhi in one kernel) per (query, allowed doc);
  *      no [B][n] block in the workspace;
- *    dense -- everything else (long documents, REF_MEANPOOL_COSINE):
+ *    dense -- everything else (REF_MEANPOOL_COSINE):
  *      the full scorer into [B][n], then a gather of the allowed columns.
  *    Both end in the row top-k and a map of row positions to
  *    id_base + ids[pos] (the list is ascending: position order is id order). */
@@ -387,7 +392,7 @@ int cbv2_search_filtered(cbv2_index* index, const cbv2_filter* filter, int32_t s
  * finite score.  out_status int32 [B]: the row's band size, or -1 when the
  * row was scored pair by pair over its whole list; m == 0 writes padding only
  * and status 0.
- *  Where CBV2_OPT_FILTER_PATH resolves to the subset path (128-slot docs),
+ *  Where CBV2_OPT_FILTER_PATH resolves to the subset path (every ld),
  *  CBV2_OPT_FILTER_BAND picks between
  *  pair -- one faithful score per (query, allowed doc), the row top-k, the id
  *    map: status -1 everywhere; and
@@ -401,8 +406,8 @@ int cbv2_search_filtered(cbv2_index* index, const cbv2_filter* filter, int32_t s
  *    status -1 and is recomputed pair by pair on the device, no host round
  *    trip, the other rows untouched.  Needs m > k and k <= 16384: other calls
  *    take `pair` (there cap is not read).  No [B][n] buffer of any kind.
- *  Where the filter path resolves to dense (long documents; m > 0.5 n under
- *  the automatic rule): every doc's faithful score into [B][n], a column
+ *  Where the filter path resolves to dense (CBV2_OPT_FILTER_PATH = 2; m >
+ *  0.5 n under the automatic rule): every doc's faithful score into [B][n], a column
  *  gather, status -1.
  * Workspace (16-B aligned, one per stream): cbv2_search_filtered_f32_
  * workspace_size(index, filter, B, lq, k, cap) bytes, computed with the
@@ -452,6 +457,9 @@ cbv2_search_filtered_f32(cbv2_index* index, const cbv2_filter* filter, const flo
  *    search call (longer queries: the caller sums the scores of 32-token
  *    blocks; the Python layer then serves per-query filters row by row).  Paths (CBV2_OPT_FILTER_PATH; the automatic rule of
  *    cbv2_search_filtered applied to M = the largest m_b):
+ *    (the subset paths serve 128-slot docs and long documents alike: the
+ *    streaming scans take ld at run time, the faithful pair kernel works in
+ *    128-token blocks)
  *    subset, bf16 -- ONE launch of the ragged streaming scan for all rows: a
  *      wave's work item is (row b, chunk of row b's list), found by a search
  *      of the table's prefix; each (query, allowed doc) pair is streamed and

@@ -7,6 +7,11 @@ synthetic index per kind (bf16, fp32-faithful, mxfp8), one GPU.
                                  [--densities 0.001,0.01,0.1,0.25,0.5,1.0] [--reps 5]
                                  [--out profiles/filter_sweep.jsonl]
     python tools/filter_sweep.py --kinds mxfp8      (-> profiles/filter_sweep_mxfp8.jsonl)
+    python tools/filter_sweep.py --ld 512 --kinds bf16,faithful,mxfp8      (-> profiles/filter_sweep_long.jsonl)
+
+--ld 256 / 512 / 1024: a long-document index of the same bytes -- --docs * 128 /
+ld full-length docs (250,000 at ld = 512), the synthetic corpus's 128-token docs
+taken ld / 128 at a time.
 
 One child process per index kind, each under its own time limit (--limit
 seconds); a child that fails or runs out of time stops the chain.  Inside a
@@ -50,14 +55,22 @@ def child(a):
     Bmax, k = max(batches), 100
     Qf = synth.make_queries(Bmax, 32, seed=1)
     planted = synth.planted_ids(max(Bmax, 8), a.docs, 10, seed=2)[:Bmax]
+    per = a.ld // 128                    # 128-token docs of the synthetic corpus per doc of the index
+    ndocs = a.docs // per
+
+    def long_docs(t, dl):
+        if per == 1:
+            return t, dl
+        return t[: ndocs * per].view(ndocs, a.ld, 128), torch.full((ndocs,), a.ld, dtype=torch.int32, device=dev)
+
     if a.kind == "faithful":
-        x, dl = synth.make_shard(0, a.docs, Qf, planted, dev, seed=0, dtype=torch.float32)
+        x, dl = long_docs(*synth.make_shard(0, a.docs, Qf, planted, dev, seed=0, dtype=torch.float32))
         ix = ColbertIndex.faithful_f32(x, dl)
         del x
         torch.cuda.empty_cache()
         Qall = Qf.to(dev)
     else:
-        tok, dl = synth.make_shard(0, a.docs, Qf, planted, dev, seed=0)
+        tok, dl = long_docs(*synth.make_shard(0, a.docs, Qf, planted, dev, seed=0))
         if a.kind == "mxfp8":
             ix = ColbertIndex.mxfp8(tok, dl)
             del tok
@@ -65,6 +78,7 @@ def child(a):
         else:
             ix = ColbertIndex(tok, dl)
         Qall = Qf.to(dev, torch.bfloat16)
+    a.docs = ndocs                       # from here on: the docs of the index
     rng = np.random.default_rng(5)
     out = open(a.out, "a")
 
@@ -100,16 +114,17 @@ def child(a):
                     t, res[n] = timed(fn)
                     if r:
                         ts[n].append(t)
-            rec = {"kind": a.kind, "docs": a.docs, "B": B, "density": s, "m": m, "k": k, "reps": a.reps,
+            rec = {"kind": a.kind, "docs": a.docs, "ld": a.ld, "B": B, "density": s, "m": m, "k": k, "reps": a.reps,
                    "ms": {n: round(statistics.median(v), 4) for n, v in ts.items()},
-                   "min_ms": {n: round(min(v), 4) for n, v in ts.items()}, **skipped}
+                   "min_ms": {n: round(min(v), 4) for n, v in ts.items()},
+                   "max_ms": {n: round(max(v), 4) for n, v in ts.items()}, **skipped}
             if "subset" in res and "dense" in res:
                 rec["identical"] = bool(torch.equal(res["subset"][0], res["dense"][0])
                                         and torch.equal(res["subset"][1], res["dense"][1]))
             if "subset" in ts:
                 # bytes of a doc: hi (+ lo) bf16 tokens; mxfp8: e4m3 tokens + 2 scale bytes per token
-                per_doc = 128 * 128 + 256 if a.kind == "mxfp8" else 128 * 128 * 2 * (2 if a.kind == "faithful" else 1)
-                flop = 2.0 * B * 32 * m * 128 * 128 * (3 if a.kind == "faithful" else 1)
+                per_doc = per * (128 * 128 + 256 if a.kind == "mxfp8" else 128 * 128 * 2 * (2 if a.kind == "faithful" else 1))
+                flop = 2.0 * B * 32 * m * a.ld * 128 * (3 if a.kind == "faithful" else 1)
                 peak = PEAK_FP8_TFLOPS if a.kind == "mxfp8" else PEAK_BF16_TFLOPS
                 sec = rec["ms"]["subset"] * 1e-3
                 rec["subset_allowed_gb"] = round(m * per_doc / 1e9, 4)
@@ -134,7 +149,8 @@ def child(a):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--docs", type=int, default=1_000_000)
+    ap.add_argument("--docs", type=int, default=1_000_000, help="128-token docs of the corpus (the index: docs * 128 / ld)")
+    ap.add_argument("--ld", type=int, default=128, choices=(128, 256, 512, 1024), help="token slots per doc of the index")
     ap.add_argument("--kinds", default="bf16,faithful")
     ap.add_argument("--batches", default="1,16,256")
     ap.add_argument("--densities", default="0.001,0.01,0.1,0.25,0.5,1.0")
@@ -145,13 +161,15 @@ def main():
     ap.add_argument("--kind", default=None, help=argparse.SUPPRESS)     # set for the child
     a = ap.parse_args()
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "filter_sweep_mxfp8.jsonl" if a.kinds == "mxfp8" else "filter_sweep.jsonl")
+        name = "filter_sweep_long.jsonl" if a.ld != 128 else \
+            "filter_sweep_mxfp8.jsonl" if a.kinds == "mxfp8" else "filter_sweep.jsonl"
+        a.out = os.path.join(ROOT, "profiles", name)
     if a.kind is not None:
         return child(a)
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     open(a.out, "w").close()
     for kind in a.kinds.split(","):
-        cmd = [sys.executable, os.path.abspath(__file__), "--kind", kind, "--docs", str(a.docs), "--batches", a.batches,
+        cmd = [sys.executable, os.path.abspath(__file__), "--kind", kind, "--docs", str(a.docs), "--ld", str(a.ld), "--batches", a.batches,
                "--densities", a.densities, "--reps", str(a.reps), "--pair-cap", str(a.pair_cap), "--out", a.out]
         try:
             rc = subprocess.run(cmd, timeout=a.limit).returncode
