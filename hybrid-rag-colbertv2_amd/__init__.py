@@ -17,9 +17,9 @@ def __getattr__(name):  # lazy: importing the package never touches the GPU
     if name in ("DualIndexer", "HybridRetriever", "ChunkStore", "rrf_fuse"):
         from . import hybrid
         return getattr(hybrid, name)
-    if name in ("ColbertIndex",):
-        from .index import ColbertIndex
-        return ColbertIndex
+    if name in ("ColbertIndex", "DocGroups", "group_topk_rows"):
+        from . import index
+        return getattr(index, name)
     if name in ("ShardedSearcher",):
         from .distributed import ShardedSearcher
         return ShardedSearcher

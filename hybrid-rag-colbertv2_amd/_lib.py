@@ -70,6 +70,16 @@ _SIGS = {
     "cbv2_filter_batch_destroy": (ctypes.c_int, [_p]),
     "cbv2_search_filtered_batch_workspace_size": (_sz, [_p, _p, _i32, _i32, _i32, _i32]),
     "cbv2_search_filtered_batch": (ctypes.c_int, [_p, _p, _i32, _p, _i32, _i32, _i32, _i32, _p, _sz, _p, _p, _p]),
+    "cbv2_groups_bytes": (_sz, [_i64, _i32]),
+    "cbv2_groups_build_host": (ctypes.c_int, [_p, _i64, _i32, _p, _p, _p, _p]),
+    "cbv2_groups_create": (ctypes.c_int, [_p, _p, _i32, _p, _sz, _p, ctypes.POINTER(ctypes.c_void_p)]),
+    "cbv2_groups_count": (_i64, [_p]),
+    "cbv2_groups_destroy": (ctypes.c_int, [_p]),
+    "cbv2_group_topk_workspace_size": (_sz, [_p, _i32, _i32, _i32]),
+    "cbv2_group_topk_rows": (ctypes.c_int, [_p, _p, _i64, _i32, _i32, _i32, _p, _sz, _p, _p, _p, _p, _p]),
+    "cbv2_search_grouped_workspace_size": (_sz, [_p, _p, _i32, _i32, _i32, _i32, _i32]),
+    "cbv2_search_grouped": (ctypes.c_int, [_p, _p, _i32, _p, _i32, _i32, _i32, _i32, _i32, _p, _sz, _p, _p, _p, _p,
+                                           _p]),
     "cbv2_rerank": (ctypes.c_int, [_p, _p, _i32, _i32, _p, _i32, _i32, _p, _p, _p, _p]),
     "cbv2_rerank_workspace_bytes": (_sz, [_i32, _i32]),
     "cbv2_rerank_ws": (ctypes.c_int, [_p, _p, _i32, _i32, _p, _i32, _i32, _p, _sz, _p, _p, _p, _p]),

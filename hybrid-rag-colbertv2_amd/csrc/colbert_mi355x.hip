@@ -5934,6 +5934,22 @@ struct cbv2_filter_batch {
   const int32_t* table = nullptr;
 };
 
+// A grouping of a shard's chunks (cbv2_groups_create): the member chunks
+// sorted by group in the caller's device buffer.  Segment s of `order` --
+// positions [offsets[s], offsets[s + 1]) -- holds the chunks of the caller's
+// group labels[s], ascending local id; only groups with members have a
+// segment.  Read-only after creation; bound to the index's n, id_base, device.
+struct cbv2_groups {
+  int device = 0;
+  int64_t n = 0, id_base = 0;
+  int32_t G = 0;                      // the caller's group count
+  int64_t members = 0, largest = 0;   // chunks in some group; the largest group's size
+  int32_t groups = 0;                 // G': groups with at least one member
+  const int32_t* order = nullptr;     // [members] local chunk ids
+  const int32_t* offsets = nullptr;   // [G' + 1]
+  const int32_t* labels = nullptr;    // [G']
+};
+
 namespace {
 thread_local char g_err[512] = "";
 
@@ -7931,6 +7947,336 @@ FilterPlan filter_batch_plan(const cbv2_index* ix, const cbv2_filter_batch* fb, 
                              int32_t scorer) {
   return filter_plan_m(ix, fb->max_m, true, B, lq, scorer);
 }
+
+// ---------------------------------------------------------------------------
+// Grouped search (cbv2_groups_*, cbv2_group_topk_rows, cbv2_search_grouped):
+// the top-k GROUPS of a score matrix [B][n], a group's score the maximum of its
+// chunks', and each selected group's best r chunks.  Three steps over the
+// sorted member list of cbv2_groups (order / offsets / labels):
+//   group_reduce_kernel   scores [B][n] -> keys [B][G'], the order-preserving
+//                         f2u bits of every segment's maximum;
+//   group_rows_kernel     keys -> the float row, in place; then the existing row
+//                         top-k over [B][G'] (positions: id_base 0);
+//   group_finish_kernel   per (query, selected slot): position -> labels[pos],
+//                         the best r chunks of that segment, the padding.
+// Max is exact and commutative, and keys carry the scores' own bits: nothing
+// here depends on the tile size, the grid or the order of the atomics.
+// ---------------------------------------------------------------------------
+constexpr int kGrpThreads = 256;
+constexpr int kGrpPer = 4;                        // order positions per thread
+constexpr int kGrpTile = kGrpThreads * kGrpPer;   // order positions per workgroup
+constexpr int kGrpRows = 8;                       // rows b one workgroup reduces with one read of its order entries
+constexpr int kGrpMaxR = 8;                       // chunks reported per group, at most
+constexpr int kGfThreads = 512;                   // group_finish_kernel's workgroup
+constexpr int kGfUnroll = 8;                      // segment positions in flight per thread
+
+// Work is split over fixed tiles of ORDER POSITIONS, not over groups: one
+// group of half the corpus beside singletons costs every workgroup the same.
+// A thread owns kGrpPer positions (lane-consecutive, so a wave reads 64
+// consecutive order entries: coalesced score loads where a group is a
+// contiguous id range, a gather otherwise), finds each position's segment once
+// (a binary search of offsets) and reuses id, segment and the scan's links for
+// kGrpRows rows.  Per row: a segmented inclusive max over the wave's 64
+// positions (shuffles; segments are sorted, so "same segment d lanes below"
+// links a contiguous run), and the last lane of every run publishes the run's
+// maximum: a plain store when the whole segment lies inside the wave's 64
+// positions (no other wave touches that key), else a 32-bit atomicMax on the
+// key (zeroed by the call; f2u of any score is > 0).
+__global__ __launch_bounds__(kGrpThreads) void group_reduce_kernel(const float* __restrict__ scores, int64_t ld, int B,
+                                                                   const int32_t* __restrict__ order,
+                                                                   const int32_t* __restrict__ offsets,
+                                                                   int64_t members, int32_t groups,
+                                                                   uint32_t* __restrict__ keys) {
+  const int lane = threadIdx.x & 63;
+  const int64_t tile0 = (int64_t)blockIdx.x * kGrpTile;
+  int32_t id[kGrpPer], seg[kGrpPer];
+  uint32_t link[kGrpPer];   // bit j: the position 2^j lanes below is in the same segment
+  int mode[kGrpPer];        // 0: nothing to publish, 1: plain store, 2: atomic max
+#pragma unroll
+  for (int u = 0; u < kGrpPer; ++u) {
+    const int64_t p = tile0 + (int64_t)u * kGrpThreads + threadIdx.x;
+    const bool live = p < members;
+    id[u] = live ? order[p] : -1;
+    int32_t lo = 0, hi = groups;   // offsets[lo] <= p < offsets[hi]
+    while (live && hi - lo > 1) {
+      const int32_t mid = lo + ((hi - lo) >> 1);
+      if ((int64_t)offsets[mid] <= p) lo = mid; else hi = mid;
+    }
+    seg[u] = live ? lo : groups;   // dead positions (past the last tile's members) form a run that publishes nothing
+    link[u] = 0u;
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+      const int32_t below = __shfl_up(seg[u], 1u << j);
+      if (lane >= (1 << j) && below == seg[u]) link[u] |= 1u << j;
+    }
+    const int32_t above = __shfl_down(seg[u], 1u);
+    const bool tail = live && (lane == 63 || above != seg[u]);
+    mode[u] = 0;
+    if (tail) {
+      const int64_t w0 = p - lane;   // the wave's first position
+      mode[u] = ((int64_t)offsets[seg[u]] >= w0 && (int64_t)offsets[seg[u] + 1] <= w0 + 64) ? 1 : 2;
+    }
+  }
+  for (int b0 = blockIdx.y * kGrpRows; b0 < B; b0 += gridDim.y * kGrpRows) {   // block-uniform
+    const int b1 = b0 + kGrpRows < B ? b0 + kGrpRows : B;
+    for (int b = b0; b < b1; ++b) {
+      const float* __restrict__ row = scores + (size_t)b * ld;
+      uint32_t key[kGrpPer];
+#pragma unroll
+      for (int u = 0; u < kGrpPer; ++u) key[u] = id[u] >= 0 ? f2u(row[id[u]]) : 0u;
+#pragma unroll
+      for (int u = 0; u < kGrpPer; ++u) {
+#pragma unroll
+        for (int j = 0; j < 6; ++j) {
+          const uint32_t below = __shfl_up(key[u], 1u << j);
+          if ((link[u] >> j) & 1u) key[u] = max(key[u], below);
+        }
+        uint32_t* dst = keys + (size_t)b * groups + (mode[u] != 0 ? seg[u] : 0);
+        if (mode[u] == 1) *dst = key[u];
+        else if (mode[u] == 2) atomicMax(dst, key[u]);
+      }
+    }
+  }
+}
+
+// keys -> the group-score row, in place (the two share the workspace block).
+__global__ __launch_bounds__(256) void group_rows_kernel(uint32_t* __restrict__ keys, int64_t total) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x)
+    keys[i] = __float_as_uint(u2f(keys[i]));
+}
+
+// Sorted insert into a descending list of kGrpMaxR keys (0 = empty slot);
+// static indices only, so the list stays in registers.
+__device__ __forceinline__ void group_best_insert(uint64_t (&l)[kGrpMaxR], uint64_t key) {
+  if (key <= l[kGrpMaxR - 1]) return;
+#pragma unroll
+  for (int i = kGrpMaxR - 1; i >= 1; --i) {
+    if (key > l[i - 1]) l[i] = l[i - 1];
+    else if (key > l[i]) l[i] = key;
+  }
+  if (key > l[0]) l[0] = key;
+}
+
+// One workgroup per (query b, selected slot j); both grid dimensions stride.
+// pos = the row top-k's position in [0, G') or -1 (padding).  One pass over the
+// segment: every thread keeps the best kGrpMaxR of the chunks it reads as
+// rank_key(score, local chunk id) -- score descending, then id ascending; -inf
+// chunks keep their ids and rank last -- then r rounds pick the largest head
+// of all lists (keys are distinct: a chunk is in one list), whose owner pops
+// it.  Segments run from 1 chunk to all n: a long one is read kGfUnroll
+// positions per thread at a time, the scores of this step under the order
+// entries of the next (two dependent loads per chunk: the loop is bound by
+// their latency, not by bytes); one of at most 64 chunks by one wave alone.
+__global__ __launch_bounds__(kGfThreads) void group_finish_kernel(const float* __restrict__ scores, int64_t ld, int B,
+                                                                  int k, int r, const int32_t* __restrict__ order,
+                                                                  const int32_t* __restrict__ offsets,
+                                                                  const int32_t* __restrict__ labels, int32_t groups,
+                                                                  int64_t id_base, const int32_t* __restrict__ sel_pos,
+                                                                  int32_t* __restrict__ out_groups,
+                                                                  int32_t* __restrict__ out_ids,
+                                                                  float* __restrict__ out_cs) {
+  __shared__ uint64_t s_best[kGfThreads / 64];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  for (int b = blockIdx.y; b < B; b += gridDim.y) {
+    for (int j = blockIdx.x; j < k; j += gridDim.x) {   // (b, j): block-uniform
+      const size_t slot = (size_t)b * k + j;
+      const int32_t pos = sel_pos[slot];
+      if (pos < 0 || pos >= groups) {   // past min(k, G'): padding
+        if (tid == 0) out_groups[slot] = -1;
+        if (tid < r) {
+          out_ids[slot * r + tid] = -1;
+          out_cs[slot * r + tid] = neg_inf();
+        }
+        continue;
+      }
+      const int64_t beg = offsets[pos], end = offsets[pos + 1];
+      const float* __restrict__ row = scores + (size_t)b * ld;
+      if (end - beg <= 64) {   // block-uniform.  A short segment (the common document) is one wave's work: one
+                               // chunk per lane, no list, no LDS, no barrier; the other waves move on
+        if (wave == 0) {
+          const int64_t p = beg + lane;
+          const int32_t id = p < end ? order[p] : -1;
+          uint64_t key = id >= 0 ? rank_key(row[id], (uint32_t)id) : 0ull;
+          if (lane == 0) out_groups[slot] = labels[pos];
+          for (int t = 0; t < r; ++t) {
+            uint64_t m = key;
+#pragma unroll
+            for (int d = 32; d >= 1; d >>= 1) {
+              const uint64_t o = __shfl_xor((unsigned long long)m, d);
+              m = o > m ? o : m;
+            }
+            if (key == m) key = 0ull;   // the owner drops it (m == 0: the segment is used up)
+            if (lane == 0) {
+              out_ids[slot * r + t] = m != 0ull ? (int32_t)(id_base + (int64_t)(~(uint32_t)m)) : -1;
+              out_cs[slot * r + t] = m != 0ull ? u2f((uint32_t)(m >> 32)) : neg_inf();
+            }
+          }
+        }
+        continue;
+      }
+      uint64_t l[kGrpMaxR];
+#pragma unroll
+      for (int i = 0; i < kGrpMaxR; ++i) l[i] = 0ull;
+      constexpr int64_t kStep = (int64_t)kGfThreads * kGfUnroll;
+      // Loads are unconditional on positions clamped to the segment's last one (in bounds, and the
+      // repeats hit the cache); only the insert asks whether the position was a real one.
+      const int64_t last = end - 1;
+      int32_t next[kGfUnroll];   // the order entries of the next step, loaded under this step's score loads
+#pragma unroll
+      for (int u = 0; u < kGfUnroll; ++u) {
+        const int64_t p = beg + (int64_t)u * kGfThreads + tid;
+        next[u] = order[p < last ? p : last];
+      }
+      for (int64_t p0 = beg; p0 < end; p0 += kStep) {   // block-uniform
+        int32_t id[kGfUnroll];
+        float v[kGfUnroll];
+#pragma unroll
+        for (int u = 0; u < kGfUnroll; ++u) {
+          id[u] = next[u];
+          const int64_t p = p0 + kStep + (int64_t)u * kGfThreads + tid;
+          next[u] = order[p < last ? p : last];
+        }
+#pragma unroll
+        for (int u = 0; u < kGfUnroll; ++u) v[u] = row[id[u]];
+#pragma unroll
+        for (int u = 0; u < kGfUnroll; ++u)
+          if (p0 + (int64_t)u * kGfThreads + tid < end) group_best_insert(l, rank_key(v[u], (uint32_t)id[u]));
+      }
+      if (tid == 0) out_groups[slot] = labels[pos];
+      for (int t = 0; t < r; ++t) {   // block-uniform
+        uint64_t m = l[0];
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) {
+          const uint64_t o = __shfl_xor((unsigned long long)m, d);
+          m = o > m ? o : m;
+        }
+        if (lane == 0) s_best[wave] = m;
+        __syncthreads();
+        m = s_best[0];
+#pragma unroll
+        for (int w = 1; w < kGfThreads / 64; ++w) m = s_best[w] > m ? s_best[w] : m;
+        __syncthreads();   // every wave has read s_best before the next round writes it
+        if (m != 0ull && l[0] == m) {   // the owner pops its head
+#pragma unroll
+          for (int i = 0; i + 1 < kGrpMaxR; ++i) l[i] = l[i + 1];
+          l[kGrpMaxR - 1] = 0ull;
+        }
+        if (tid == 0) {   // past the group's size: -1 / -inf
+          out_ids[slot * r + t] = m != 0ull ? (int32_t)(id_base + (int64_t)(~(uint32_t)m)) : -1;
+          out_cs[slot * r + t] = m != 0ull ? u2f((uint32_t)(m >> 32)) : neg_inf();
+        }
+      }
+    }
+  }
+}
+
+// No group has a member (or the shard is empty): the four outputs' padding.
+__global__ __launch_bounds__(256) void group_fill_empty_kernel(float* __restrict__ out_s, int32_t* __restrict__ out_g,
+                                                               int64_t slots, int32_t* __restrict__ out_ids,
+                                                               float* __restrict__ out_cs, int r) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < slots * r; i += (int64_t)gridDim.x * blockDim.x) {
+    if (i < slots) {
+      out_s[i] = neg_inf();
+      out_g[i] = -1;
+    }
+    out_ids[i] = -1;
+    out_cs[i] = neg_inf();
+  }
+}
+
+// Workspace of the selection: the keys / group-score rows [B][G'], the row
+// top-k's positions [B][k] and the row top-k's own workspace, each rounded up
+// to 256 B.
+struct GroupWs {
+  uint32_t* keys = nullptr;
+  int32_t* pos = nullptr;
+  void* tk = nullptr;
+  size_t tk_bytes = 0;
+};
+
+size_t group_ws_layout(const cbv2_groups* g, int32_t B, int32_t k, uint8_t* base, GroupWs* w) {
+  size_t off = 0;
+  auto take = [&](size_t bytes) -> uint8_t* {
+    uint8_t* p = base ? base + off : nullptr;
+    off += (bytes + 255) & ~(size_t)255;
+    return p;
+  };
+  const size_t gp = (size_t)(g->groups > 0 ? g->groups : 1);
+  w->keys = (uint32_t*)take((size_t)B * gp * sizeof(uint32_t));
+  w->pos = (int32_t*)take((size_t)B * k * sizeof(int32_t));
+  w->tk_bytes = g->groups > 0 ? topk_ws_bytes(B, g->groups) : 0;
+  w->tk = take(w->tk_bytes);
+  return off;
+}
+
+// The argument checks the two grouped compute calls share (before any launch).
+int check_group_args(const cbv2_groups* g, int32_t B, int32_t k, int32_t r, const float* out_scores,
+                     const int32_t* out_groups, const int32_t* out_ids, const float* out_chunk_scores) {
+  CBV2_REQUIRE(g != nullptr, "null groups handle");
+  CBV2_REQUIRE(B >= 1, "B must be >= 1 (got %d)", B);
+  CBV2_REQUIRE(k >= 1, "k must be >= 1 (got %d)", k);
+  CBV2_REQUIRE(r >= 1 && r <= kGrpMaxR, "r must be in [1, %d] (got %d)", kGrpMaxR, r);
+  CBV2_REQUIRE(out_scores && out_groups && out_ids && out_chunk_scores, "null outputs");
+  return CBV2_OK;
+}
+
+int group_select_impl(const cbv2_groups* g, const float* scores, int64_t ld, int32_t B, int32_t k, int32_t r,
+                      const GroupWs& w, float* out_scores, int32_t* out_groups, int32_t* out_ids,
+                      float* out_chunk_scores, hipStream_t st) {
+  if (g->groups == 0 || g->n == 0) {   // padding only
+    const int64_t slots = (int64_t)B * k;
+    const int64_t gx = std::min<int64_t>((slots * r + 255) / 256, 65535);
+    hipLaunchKernelGGL(group_fill_empty_kernel, dim3((unsigned)gx), dim3(256), 0, st, out_scores, out_groups, slots,
+                       out_ids, out_chunk_scores, r);
+    return launch_check("group_fill_empty_kernel");
+  }
+  const int64_t total = (int64_t)B * g->groups;
+  CBV2_HIP(hipMemsetAsync(w.keys, 0, (size_t)total * sizeof(uint32_t), st));
+  const int64_t tiles = (g->members + kGrpTile - 1) / kGrpTile;
+  const int64_t gy = std::min<int64_t>((B + kGrpRows - 1) / kGrpRows, 65535);
+  hipLaunchKernelGGL(group_reduce_kernel, dim3((unsigned)tiles, (unsigned)gy), dim3(kGrpThreads), 0, st, scores, ld, B,
+                     g->order, g->offsets, g->members, g->groups, w.keys);
+  int rc = launch_check("group_reduce_kernel");
+  if (rc) return rc;
+  hipLaunchKernelGGL(group_rows_kernel, dim3((unsigned)std::min<int64_t>((total + 255) / 256, 65535)), dim3(256), 0, st,
+                     w.keys, total);
+  if ((rc = launch_check("group_rows_kernel"))) return rc;
+  // the group rows' top-k: positions of the non-empty groups (ascending group index, so the row
+  // top-k's tie rule -- lower position first -- is the lower group index)
+  rc = topk_impl((const float*)w.keys, B, g->groups, g->groups, k, 0, w.tk, w.tk_bytes, out_scores, w.pos, st,
+                 g->device);
+  if (rc) return rc;
+  hipLaunchKernelGGL(group_finish_kernel, dim3((unsigned)std::min<int32_t>(k, 1 << 20), (unsigned)std::min(B, 65535)),
+                     dim3(kGfThreads), 0, st, scores, ld, B, k, r, g->order, g->offsets, g->labels, g->groups,
+                     g->id_base, w.pos, out_groups, out_ids, out_chunk_scores);
+  return launch_check("group_finish_kernel");
+}
+
+// Workspace of cbv2_search_grouped: the scan's counter block, the selection's
+// workspace, the score block [B][n] and, where the index has a residual (the
+// faithful scorer may be asked for), the query split of cbv2_score_f32.
+struct GroupSearchWs {
+  int* ctr = nullptr;
+  GroupWs sel;
+  float* S = nullptr;
+  uint8_t* f32 = nullptr;
+};
+
+size_t group_search_layout(const cbv2_index* ix, const cbv2_groups* g, int32_t B, int32_t lq, int32_t k,
+                           int32_t scorer, uint8_t* base, GroupSearchWs* w) {
+  size_t off = kCtrBytes;
+  w->ctr = (int*)base;
+  off += group_ws_layout(g, B, k, base ? base + off : nullptr, &w->sel);
+  w->S = (float*)(base ? base + off : nullptr);
+  off += ((size_t)B * (size_t)(ix->n > 0 ? ix->n : 1) * sizeof(float) + 255) & ~(size_t)255;
+  w->f32 = nullptr;
+  if (ix->resid != nullptr && scorer == CBV2_SCORER_MAXSIM && lq <= kLqMax) {
+    F32Ws f;
+    w->f32 = base ? base + off : nullptr;
+    off += f32_ws_layout(ix, CBV2_F32_SCORE, B, lq, 0, nullptr, &f);
+  }
+  return off;
+}
 }  // namespace
 
 extern "C" {
@@ -8510,6 +8856,149 @@ int cbv2_search_filtered_batch(cbv2_index* ix, const cbv2_filter_batch* fb, int3
   hipLaunchKernelGGL(fb_map_ids_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, out_ids, B, k,
                      fb->table, fb->id_base);
   return launch_check("fb_map_ids_kernel");
+}
+
+// Grouped search ------------------------------------------------------------
+static size_t groups_buf_layout(int64_t n, int32_t G, size_t* off_offsets, size_t* off_labels) {
+  auto r256 = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t o1 = r256((size_t)n * sizeof(int32_t));
+  const size_t o2 = o1 + r256(((size_t)G + 1) * sizeof(int32_t));
+  if (off_offsets) *off_offsets = o1;
+  if (off_labels) *off_labels = o2;
+  return o2 + r256((size_t)G * sizeof(int32_t));
+}
+
+size_t cbv2_groups_bytes(int64_t n, int32_t G) {
+  if (n < 0 || n > 0x7fffffffLL || G < 1) return 0;
+  return groups_buf_layout(n, G, nullptr, nullptr);
+}
+
+int cbv2_groups_create(const cbv2_index* ix, const int32_t* group_of, int32_t G, void* buf, size_t buf_bytes,
+                       void* stream, cbv2_groups** out) {
+  CBV2_REQUIRE(out != nullptr, "null output handle pointer");
+  *out = nullptr;
+  CBV2_REQUIRE(ix != nullptr, "null index");
+  CBV2_REQUIRE(ix->n <= 0x7fffffffLL, "too many docs for an int32 id list");
+  CBV2_REQUIRE(G >= 1, "G must be >= 1 (got %d)", G);
+  CBV2_REQUIRE(ix->n == 0 || group_of != nullptr, "null group_of");
+  size_t off_offsets, off_labels;
+  const size_t need = groups_buf_layout(ix->n, G, &off_offsets, &off_labels);
+  CBV2_REQUIRE(buf != nullptr && buf_bytes >= need && aligned16(buf), "groups buffer too small or misaligned (%zu < %zu)",
+               buf_bytes, need);
+  // the host half first: a bad group_of is reported before anything touches the device
+  std::vector<int32_t> order, offsets, labels;
+  try {
+    order.resize((size_t)ix->n);
+    offsets.resize((size_t)G + 1);
+    labels.resize((size_t)G);
+  } catch (const std::bad_alloc&) {
+    return fail(CBV2_EINVAL, "no host memory for a grouping of %lld chunks in %d groups", (long long)ix->n, G);
+  }
+  int64_t out3[3] = {0, 0, 0};
+  if (int rc = cbv2_groups_build_host(group_of, ix->n, G, order.data(), offsets.data(), labels.data(), out3)) return rc;
+  DeviceGuard dg(ix->device);
+  if (!dg.ok) return fail(CBV2_EHIP, "cannot select device %d", ix->device);
+  hipStream_t st = (hipStream_t)stream;
+  uint8_t* base = (uint8_t*)buf;
+  if (out3[0] > 0)
+    CBV2_HIP(hipMemcpyAsync(base, order.data(), (size_t)out3[0] * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  CBV2_HIP(hipMemcpyAsync(base + off_offsets, offsets.data(), ((size_t)out3[1] + 1) * sizeof(int32_t),
+                          hipMemcpyHostToDevice, st));
+  if (out3[1] > 0)
+    CBV2_HIP(hipMemcpyAsync(base + off_labels, labels.data(), (size_t)out3[1] * sizeof(int32_t), hipMemcpyHostToDevice,
+                            st));
+  CBV2_HIP(hipStreamSynchronize(st));   // the host arrays go out of scope: wait for the copies
+  auto* g = new cbv2_groups;
+  g->device = ix->device;
+  g->n = ix->n;
+  g->id_base = ix->id_base;
+  g->G = G;
+  g->members = out3[0];
+  g->groups = (int32_t)out3[1];
+  g->largest = out3[2];
+  g->order = (const int32_t*)base;
+  g->offsets = (const int32_t*)(base + off_offsets);
+  g->labels = (const int32_t*)(base + off_labels);
+  *out = g;
+  return CBV2_OK;
+}
+
+int64_t cbv2_groups_count(const cbv2_groups* g) { return g ? g->groups : -1; }
+
+int cbv2_groups_destroy(cbv2_groups* g) {
+  delete g;
+  return CBV2_OK;
+}
+
+size_t cbv2_group_topk_workspace_size(const cbv2_groups* g, int32_t B, int32_t k, int32_t r) {
+  if (!g || B < 1 || k < 1 || r < 1 || r > kGrpMaxR) return 0;
+  GroupWs w;
+  return group_ws_layout(g, B, k, nullptr, &w);
+}
+
+int cbv2_group_topk_rows(const cbv2_groups* g, const float* scores, int64_t ld, int32_t B, int32_t k, int32_t r,
+                         void* ws, size_t ws_bytes, float* out_scores, int32_t* out_groups, int32_t* out_ids,
+                         float* out_chunk_scores, void* stream) {
+  if (int rc = check_group_args(g, B, k, r, out_scores, out_groups, out_ids, out_chunk_scores)) return rc;
+  CBV2_REQUIRE(g->members == 0 || scores != nullptr, "null scores");
+  CBV2_REQUIRE(ld >= g->n, "ld (%lld) < n (%lld)", (long long)ld, (long long)g->n);
+  GroupWs w;
+  const size_t need = group_ws_layout(g, B, k, nullptr, &w);
+  CBV2_REQUIRE(ws != nullptr && ws_bytes >= need && aligned16(ws), "workspace too small or misaligned (%zu < %zu)",
+               ws_bytes, need);
+  group_ws_layout(g, B, k, (uint8_t*)ws, &w);
+  DeviceGuard dg(g->device);
+  if (!dg.ok) return fail(CBV2_EHIP, "cannot select device %d", g->device);
+  return group_select_impl(g, scores, ld, B, k, r, w, out_scores, out_groups, out_ids, out_chunk_scores,
+                           (hipStream_t)stream);
+}
+
+size_t cbv2_search_grouped_workspace_size(const cbv2_index* ix, const cbv2_groups* g, int32_t B, int32_t lq, int32_t k,
+                                          int32_t r, int32_t scorer) {
+  if (!ix || !g || B < 1 || lq < 1 || k < 1 || r < 1 || r > kGrpMaxR) return 0;
+  GroupSearchWs w;
+  return group_search_layout(ix, g, B, lq, k, scorer, nullptr, &w);
+}
+
+int cbv2_search_grouped(cbv2_index* ix, const cbv2_groups* g, int32_t scorer, const void* Q, int32_t q_dtype, int32_t B,
+                        int32_t lq, int32_t k, int32_t r, void* ws, size_t ws_bytes, float* out_scores,
+                        int32_t* out_groups, int32_t* out_ids, float* out_chunk_scores, void* stream) {
+  CBV2_REQUIRE(g != nullptr, "null groups handle");
+  CBV2_REQUIRE(ix != nullptr, "null index");
+  const bool faithful = scorer == CBV2_SCORER_MAXSIM && q_dtype == CBV2_DTYPE_F32 && ix->resid != nullptr;
+  if (faithful) {
+    CBV2_REQUIRE(Q != nullptr && aligned16(Q), "query pointer must be non-null and 16-byte aligned");
+    CBV2_REQUIRE(B >= 1 && B <= 65535, "B must be in [1, 65535] (got %d)", B);
+    CBV2_REQUIRE(lq >= 1 && lq <= kLqMax, "lq must be in [1, %d] (got %d)", kLqMax, lq);
+  } else if (int rc = check_query(ix, scorer, Q, q_dtype, B, lq)) {
+    return rc;
+  }
+  CBV2_REQUIRE(lq <= kLqMax, "a grouped search takes at most %d query tokens (got %d)", kLqMax, lq);
+  CBV2_REQUIRE(g->n == ix->n && g->id_base == ix->id_base && g->device == ix->device,
+               "the groups were created for another index (n %lld / %lld, id_base %lld / %lld, device %d / %d)",
+               (long long)g->n, (long long)ix->n, (long long)g->id_base, (long long)ix->id_base, g->device, ix->device);
+  if (int rc = check_group_args(g, B, k, r, out_scores, out_groups, out_ids, out_chunk_scores)) return rc;
+  GroupSearchWs w;
+  const size_t need = group_search_layout(ix, g, B, lq, k, scorer, nullptr, &w);
+  CBV2_REQUIRE(ws != nullptr && ws_bytes >= need && aligned16(ws), "workspace too small or misaligned (%zu < %zu)",
+               ws_bytes, need);
+  group_search_layout(ix, g, B, lq, k, scorer, (uint8_t*)ws, &w);
+  DeviceGuard dg(ix->device);
+  if (!dg.ok) return fail(CBV2_EHIP, "cannot select device %d", ix->device);
+  hipStream_t st = (hipStream_t)stream;
+  if (g->groups > 0 && ix->n > 0) {   // (no member anywhere: padding only, no scan)
+    int rc;
+    if (faithful) {   // cbv2_score_f32's full faithful scan: no band
+      F32Ws f;
+      f32_ws_layout(ix, CBV2_F32_SCORE, B, lq, 0, w.f32, &f);
+      if ((rc = split_queries(ix, (const float*)Q, B, lq, &f, st))) return rc;
+      rc = launch_rescore(ix, &f, B, lq, nullptr, nullptr, ix->n, 0, w.S, ix->n, st);
+    } else {
+      rc = score_impl(ix, scorer, Q, B, lq, w.S, ix->n, st, w.ctr);
+    }
+    if (rc) return rc;
+  }
+  return group_select_impl(g, w.S, ix->n, B, k, r, w.sel, out_scores, out_groups, out_ids, out_chunk_scores, st);
 }
 
 int cbv2_index_set_option(cbv2_index* ix, int32_t option, int64_t value) {

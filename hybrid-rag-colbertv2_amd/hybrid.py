@@ -89,6 +89,13 @@ class ChunkStore:
         ``HybridRetriever.retrieve(allowed_ids=...)``)."""
         return sorted(cid for cid, row in self._rows.items() if row["document_id"] == document_id)
 
+    def document_keys(self, n: int) -> List:
+        """The ``document_id`` of chunk ids ``0 .. n-1``, ``None`` where the chunk
+        or its document is unknown (the ``keys`` of ``ColbertIndex.groups`` /
+        ``JinaColBERTRetriever.make_groups``: one group per document)."""
+        rows = self._rows
+        return [rows[i]["document_id"] if i in rows else None for i in range(int(n))]
+
     def __len__(self):
         return len(self._rows)
 

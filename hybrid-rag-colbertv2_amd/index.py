@@ -306,6 +306,73 @@ class FilterBatch:
             pass
 
 
+MAX_PER_GROUP = 8   # chunks a grouped search reports per group, at most
+
+
+def group_labels(keys) -> Tuple[torch.Tensor, list]:
+    """Hashable labels, one per chunk (``None`` = in no group) -> (int32
+    ``group_of`` [n] on the host, the distinct labels).  Labels are numbered
+    densely in order of first appearance, so among groups of equal score the
+    one whose first chunk has the lower id ranks first; ``None`` maps to -1."""
+    number: dict = {}
+    out = []
+    for key in keys:
+        out.append(-1 if key is None else number.setdefault(key, len(number)))
+    return torch.tensor(out, dtype=torch.int32), list(number)
+
+
+class DocGroups:
+    """A grouping of one ``ColbertIndex``'s chunks (cbv2_groups_create): the
+    member chunks sorted by group on the host and kept in a device buffer this
+    object owns.  ``group_of`` int32 [n]: chunk i's group index in [0, G), or
+    -1 for "in no group" (never returned).  ``labels[g]`` is the caller's name
+    of group g (default: g itself); ``count`` the number of groups with at
+    least one member.  Read-only; reusable across searches and streams of that
+    index.  Creating one waits for the device once (the upload)."""
+
+    def __init__(self, index: "ColbertIndex", group_of, G: Optional[int] = None, labels: Optional[Sequence] = None):
+        L = _lib.lib()
+        self.index = index
+        group_of = torch.as_tensor(group_of).reshape(-1)
+        if group_of.is_floating_point() or group_of.dtype == torch.bool:
+            raise ValueError("group_of must hold integer group indices (-1: in no group)")
+        if group_of.numel() != index.n:
+            raise ValueError(f"group_of must hold one entry per chunk of the index ({group_of.numel()} for {index.n})")
+        wide = group_of.to("cpu", torch.int64)
+        if G is None:
+            G = max(int(wide.max()) + 1, 1) if wide.numel() else 1
+        if wide.numel() and (int(wide.min()) < -1 or int(wide.max()) >= int(G)):
+            bad = int(((wide < -1) | (wide >= int(G))).nonzero()[0])
+            raise ValueError(f"group_of[{bad}] = {int(wide[bad])} is outside [-1, {int(G)})")
+        self.G = int(G)
+        if labels is not None and len(labels) != self.G:
+            raise ValueError(f"labels must name every group ({len(labels)} for {self.G})")
+        self.labels = list(labels) if labels is not None else list(range(self.G))
+        self.group_of = wide.to(torch.int32).contiguous()
+        need = int(L.cbv2_groups_bytes(index.n, self.G))
+        self._buf = torch.empty((max(need, 16),), dtype=torch.uint8, device=index.device)
+        h = ctypes.c_void_p()
+        _lib.check(L.cbv2_groups_create(index._h, self.group_of.data_ptr() if index.n else None, self.G,
+                                        self._buf.data_ptr(), self._buf.numel(), _stream_ptr(index.device),
+                                        ctypes.byref(h)))
+        self._h = h
+        self.count = int(L.cbv2_groups_count(h))
+
+    def close(self) -> None:
+        if getattr(self, "_h", None) is not None and self._h.value:
+            _lib.lib().cbv2_groups_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __len__(self):
+        return self.count
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class ColbertIndex:
     """One shard of the corpus resident in HBM, with a C handle borrowing it.
 
@@ -856,6 +923,64 @@ class ColbertIndex:
         self.last_band = status
         return out_s, out_i
 
+    # ----------------------------------------------------------------- grouped search
+    def groups(self, keys=None, group_of=None, G: Optional[int] = None) -> DocGroups:
+        """A ``DocGroups`` of this shard: ``keys``, one hashable label per chunk
+        (``None`` = in no group; e.g. ``ChunkStore.document_keys(n)``), numbered
+        in order of first appearance -- or the raw form, ``group_of`` int [n]
+        with values in [0, G) or -1 (``G`` defaults to the largest index + 1)."""
+        if (keys is None) == (group_of is None):
+            raise ValueError("groups() takes keys or group_of, not both")
+        if keys is None:
+            return DocGroups(self, group_of, G)
+        if G is not None:
+            raise ValueError("G goes with group_of; keys number their own groups")
+        gof, labels = group_labels(keys)
+        return DocGroups(self, gof, max(len(labels), 1), labels if labels else [None])
+
+    def _check_groups(self, groups: DocGroups, per_group: int) -> int:
+        if not isinstance(groups, DocGroups):
+            raise TypeError("groups must be a DocGroups (ColbertIndex.groups)")
+        if not groups._h.value:
+            raise ValueError("the groups handle is closed")
+        per_group = int(per_group)
+        if not 1 <= per_group <= MAX_PER_GROUP:
+            raise ValueError(f"per_group must be in [1, {MAX_PER_GROUP}] (got {per_group})")
+        return per_group
+
+    def search_grouped(self, Q: torch.Tensor, k: int, groups: DocGroups, per_group: int = 1,
+                       scorer: str = "maxsim"):
+        """The top-k GROUPS (documents), each with its best ``per_group`` chunks
+        (cbv2_search_grouped; asynchronous): (scores f32 [B, k], group indices
+        int32 [B, k], global chunk ids int32 [B, k, per_group], chunk scores f32
+        [B, k, per_group]).  A group's score is its best chunk's; groups rank by
+        score, then group index; chunks by score, then id.  Padding past the
+        number of non-empty groups / a group's size: -inf / -1.  The scores are
+        the unfiltered scorer's bit for bit (the faithful scores on an
+        fp32-faithful index: its full scan, no band).  MaxSim queries of more
+        than 32 tokens take ``score()`` (the blocks' scores summed) and then
+        ``group_topk_rows``."""
+        r = self._check_groups(groups, per_group)
+        k = int(k)
+        if self._query_blocks(Q, scorer) is not None:
+            if (groups.index.n, groups.index.id_base, groups.index.device) != (self.n, self.id_base, self.device):
+                raise ValueError("the groups were created for another index")
+            return group_topk_rows(self.score(Q, scorer), k, groups, r)
+        sid = self._scorer(scorer)
+        _keep, qptr, qdt, B, lq = self._prep_query(Q, scorer)
+        L = _lib.lib()
+        need = int(L.cbv2_search_grouped_workspace_size(self._h, groups._h, B, lq, k, r, sid))
+        if self._ws is None or self._ws.numel() * 4 < need:
+            self._ws = torch.empty(((need + 3) // 4,), dtype=torch.float32, device=self.device)
+        out_s = torch.empty((B, k), dtype=torch.float32, device=self.device)
+        out_g = torch.empty((B, k), dtype=torch.int32, device=self.device)
+        out_i = torch.empty((B, k, r), dtype=torch.int32, device=self.device)
+        out_c = torch.empty((B, k, r), dtype=torch.float32, device=self.device)
+        _lib.check(L.cbv2_search_grouped(self._h, groups._h, sid, qptr, qdt, B, lq, k, r, self._ws.data_ptr(),
+                                         self._ws.numel() * 4, out_s.data_ptr(), out_g.data_ptr(), out_i.data_ptr(),
+                                         out_c.data_ptr(), _stream_ptr(self.device)))
+        return out_s, out_g, out_i, out_c
+
     def rerank(self, Q: torch.Tensor, cand: torch.Tensor, k: int):
         """Gather candidates by global id and MaxSim-rank them.
 
@@ -1127,6 +1252,39 @@ def topk_rows(scores: torch.Tensor, k: int, id_base: int = 0, sampled: bool = Tr
                                          ws.data_ptr() if need else None, need, out_s.data_ptr(),
                                          out_i.data_ptr(), _stream_ptr(dev)))
     return out_s, out_i
+
+
+def group_topk_rows(scores: torch.Tensor, k: int, groups: DocGroups, per_group: int = 1):
+    """The grouped selection on its own (cbv2_group_topk_rows): the top-k groups
+    of each row of a [B, n] score matrix over the chunks of ``groups``' index,
+    with each group's best ``per_group`` chunks; returns what
+    ``ColbertIndex.search_grouped`` returns."""
+    _require_cuda(scores, "scores")
+    if not isinstance(groups, DocGroups):
+        raise TypeError("groups must be a DocGroups (ColbertIndex.groups)")
+    if not groups._h.value:
+        raise ValueError("the groups handle is closed")
+    k, r = int(k), int(per_group)
+    if scores.dim() == 1:
+        scores = scores.unsqueeze(0)
+    scores = scores.to(torch.float32)
+    if scores.stride(1) != 1:
+        scores = scores.contiguous()
+    B, n = scores.shape
+    if n != groups.index.n:
+        raise ValueError(f"scores must be [B, {groups.index.n}] (got {tuple(scores.shape)})")
+    dev = scores.device
+    L = _lib.lib()
+    need = int(L.cbv2_group_topk_workspace_size(groups._h, B, k, r))
+    ws = torch.empty((max(need, 16),), dtype=torch.uint8, device=dev)
+    out_s = torch.empty((B, k), dtype=torch.float32, device=dev)
+    out_g = torch.empty((B, k), dtype=torch.int32, device=dev)
+    out_i = torch.empty((B, k, max(r, 1)), dtype=torch.int32, device=dev)
+    out_c = torch.empty((B, k, max(r, 1)), dtype=torch.float32, device=dev)
+    _lib.check(L.cbv2_group_topk_rows(groups._h, scores.data_ptr(), scores.stride(0) if B > 1 else max(n, 1), B, k, r,
+                                      ws.data_ptr(), ws.numel(), out_s.data_ptr(), out_g.data_ptr(),
+                                      out_i.data_ptr(), out_c.data_ptr(), _stream_ptr(dev)))
+    return out_s, out_g, out_i, out_c
 
 
 def merge_topk(scores: torch.Tensor, ids: torch.Tensor, k: int):

@@ -27,7 +27,7 @@ import torch
 
 from .config import RAGConfig
 from .encoder import encode, load_local_encoder
-from .index import ColbertIndex, DocFilter, FilterBatch, IndexBuilder, select_topk
+from .index import ColbertIndex, DocFilter, DocGroups, FilterBatch, IndexBuilder, select_topk
 
 
 class JinaColBERTRetriever:
@@ -210,6 +210,39 @@ class JinaColBERTRetriever:
         if allowed_ids is None:
             return self.corpus_embeddings.search(Q, k, scorer=self.scorer)
         return self.corpus_embeddings.search(Q, k, scorer=self.scorer, filter=self._as_filter(allowed_ids))
+
+    # ------------------------------------------------------------ grouped search
+    def make_groups(self, keys) -> DocGroups:
+        """A reusable ``DocGroups`` of the index: ``keys`` holds one hashable
+        label per chunk (its document; ``None`` = in no group, never returned),
+        e.g. ``ChunkStore.document_keys(n)``.  One device round trip."""
+        if self.corpus_embeddings is None:
+            raise RuntimeError("no index: call index() or load() first")
+        return self.corpus_embeddings.groups(keys=keys)
+
+    def search_grouped(self, query: str, k: int = 10, groups=None, per_group: int = 1) -> List[Dict]:
+        """The k best GROUPS (documents) for the query, each with its best
+        ``per_group`` chunks: [{'group': label, 'score', 'chunks':
+        [{'document_id', 'score', 'text'}, ...]}], best first; a group's score is
+        its best chunk's, and 'document_id' is the chunk id, as in ``search``.
+        ``groups``: a ``DocGroups`` (``make_groups``) or the per-chunk keys."""
+        ix = self.corpus_embeddings
+        if ix is None:
+            raise RuntimeError("no index: call index() or load() first")
+        if groups is None:
+            raise ValueError("search_grouped needs groups (make_groups) or the chunks' keys")
+        grp = groups if isinstance(groups, DocGroups) else self.make_groups(groups)
+        kk = min(int(k), grp.count)
+        if kk <= 0:
+            return []
+        q = self._encode_query(query)
+        scores, gidx, ids, cscores = ix.search_grouped(q.unsqueeze(0), kk, grp, per_group=per_group,
+                                                       scorer=self.scorer)
+        scores, gidx, ids, cscores = scores[0].tolist(), gidx[0].tolist(), ids[0].tolist(), cscores[0].tolist()
+        return [{"group": grp.labels[g], "score": float(s),
+                 "chunks": [{"document_id": int(i), "score": float(c), "text": self.corpus[i] if self.corpus else None}
+                            for i, c in zip(row_i, row_c) if i >= 0]}
+                for s, g, row_i, row_c in zip(scores, gidx, ids, cscores) if g >= 0]
 
     # ------------------------------------------------------------ rerank
     def rerank(self, query: str, documents: List[str], k: int = 10) -> List[Dict]:

@@ -490,6 +490,109 @@ int cbv2_search_filtered_batch(cbv2_index* index, const cbv2_filter_batch* fb, i
                                int32_t q_dtype, int32_t B, int32_t lq, int32_t k, void* workspace,
                                size_t workspace_bytes, float* out_scores, int32_t* out_ids, void* stream);
 
+/* Grouped search (no reference counterpart: the reference ranks chunks, but its
+ * chunks carry a document_id -- local_rag_complete.py's ChunkStore -- and a RAG
+ * application asks for DOCUMENTS; one long document can own every slot of a
+ * chunk top-k).  The top-k groups, each with its best chunks.  Everything here
+ * is exact: no tolerance, no over-fetch.
+ *  A grouping assigns every LOCAL chunk i a group index group_of[i] in [0, G),
+ *  or -1 for "in no group": such a chunk is never returned (a filter composes
+ *  with grouping by putting -1 on disallowed chunks).  Groups need not be
+ *  contiguous id ranges; groups without members are allowed; G' = the number
+ *  of groups with at least one member.  For each query b:
+ *    group score   the maximum of the scorer's scores of the group's chunks --
+ *                  the unfiltered scorer's bits (cbv2_score; cbv2_score_f32 for
+ *                  a faithful search);
+ *    group order   group score descending, then group index ascending;
+ *    chunks        for each of the top-k groups its best r chunks (1 <= r <= 8),
+ *                  score descending, then chunk id ascending;
+ *    empty docs    a chunk with doclens == 0 scores -inf, keeps its id and
+ *                  ranks after every finite chunk of its group; a group whose
+ *                  chunks all score -inf ranks after every finite group and
+ *                  keeps its index and chunk ids (the filters' convention).
+ *  Outputs: out_scores f32 [B][k] (-inf past min(k, G')), out_groups int32
+ *  [B][k] (the caller's group index; -1 past min(k, G')), out_ids int32
+ *  [B][k][r] (GLOBAL chunk ids; -1 past the group's size and in padded
+ *  groups), out_chunk_scores f32 [B][k][r] (-inf where out_ids is -1);
+ *  out_chunk_scores[b][j][0] has the bits of out_scores[b][j].  Any k >= 1, as
+ *  in cbv2_search (k > 1024: the multi-pass selection).
+ *  - cbv2_groups_build_host (HOST pointers, no GPU): a stable counting sort of
+ *    the member chunks.  order int32 [n]: the member chunks grouped by group,
+ *    ascending id inside a group, the first out3[0] entries valid; offsets
+ *    int32 [G + 1]: offsets[0 .. G'] the segment bounds over the non-empty
+ *    groups in ascending group index; labels int32 [G]: labels[0 .. G') the
+ *    caller's indices of those groups; out3 int64 [3] = {members, G', largest
+ *    group}.  A value < -1 or >= G is CBV2_EINVAL, the message names the first
+ *    offending position, and no output has been written.  G >= 1,
+ *    n <= 0x7fffffff.
+ *  - cbv2_groups_create validates group_of (HOST int32 [n], n the index's,
+ *    read during the call only) with the builder before anything touches the
+ *    device, uploads the three arrays into `buf`, a caller-owned DEVICE buffer
+ *    of cbv2_groups_bytes(n, G) bytes (16-B aligned) the handle borrows until
+ *    cbv2_groups_destroy, and WAITS on `stream` for the copies: NOT capturable,
+ *    like the filter batch's create.  The handle is read-only afterwards
+ *    (several streams may share it) and remembers the index's n, id_base and
+ *    device: passing it with an index that differs in any of those is
+ *    CBV2_EINVAL.  cbv2_groups_count: G'.
+ *  - cbv2_group_topk_rows: the selection on its own (as cbv2_topk_rows is to
+ *    cbv2_search), over any score matrix whose row b is scores[b * ld + i],
+ *    i < n (long queries' summed blocks, external scorers); columns at or past
+ *    n are never read, chunks outside every group never influence a result.
+ *    Workspace: cbv2_group_topk_workspace_size(groups, B, k, r) bytes.
+ *  - cbv2_search_grouped: the scorer's scores of every chunk into a [B][n]
+ *    block of the workspace, then the same selection.  Query types, scorers
+ *    and index kinds: those of cbv2_search (bf16, MXFP8, REF_MEANPOOL_COSINE,
+ *    ld = 128 / 256 / 512 / 1024); on an fp32-faithful index with q_dtype
+ *    CBV2_DTYPE_F32 (Q f32 [B][lq][128]) the scores are cbv2_score_f32's: the
+ *    full faithful scan, no band.  lq <= 32 for every scorer.  Workspace:
+ *    cbv2_search_grouped_workspace_size(index, groups, B, lq, k, r, scorer).
+ *  Both compute calls are asynchronous with no host round trip, and both may
+ *  be issued on a stream that is capturing a hipGraph when the groups handle
+ *  was created before the capture: every replay recomputes them from the
+ *  buffers' contents at replay time and zeroes the keys it folds into in the
+ *  workspace (tests/test_gpu_group.py replays them over a poisoned workspace
+ *  and poisoned outputs).  Every argument is checked on the host before any
+ *  launch: null handles, a handle of another index, k < 1, r outside [1, 8],
+ *  null outputs, a short or misaligned (16 B) workspace.  G' == 0 or n == 0
+ *  writes the padding only and launches no scan.  Workspaces, one per stream,
+ *  with r256 = round up to 256 B: the selection takes r256(4 B G') for the
+ *  keys / group rows + r256(4 B k) for the selected positions + the row
+ *  top-k's workspace of (B, G'); the search adds the scan's counter block in
+ *  front, r256(4 B n) for the scores and, on an fp32-faithful index, the query
+ *  split of cbv2_score_f32.  The *_size functions are authoritative (0 for a
+ *  null handle or a B, lq, k, r out of range).
+ *  How: the scores are reduced over fixed tiles of `order` positions (not over
+ *  groups: a group of half the corpus beside singletons stays balanced) by a
+ *  segmented max inside each wave, segments that cross a wave combining with a
+ *  32-bit atomic max on the order-preserving score bits; the existing row
+ *  top-k ranks the [B][G'] group rows; one workgroup per (query, selected
+ *  group) then picks that group's best r chunks in one pass over its segment.
+ * (Their guard-band tests are in tests/test_gpu_group.py, not the table of
+ * tests/test_gpu_bounds.py: hence the return types on lines of their own.)  */
+typedef struct cbv2_groups cbv2_groups;
+size_t cbv2_groups_bytes(int64_t n, int32_t G);
+int
+cbv2_groups_build_host(const int32_t* group_of, int64_t n, int32_t G, int32_t* order, int32_t* offsets,
+                           int32_t* labels, int64_t* out3);
+int
+cbv2_groups_create(const cbv2_index* index, const int32_t* group_of, int32_t G, void* buf, size_t buf_bytes,
+                       void* stream, cbv2_groups** out);
+int64_t cbv2_groups_count(const cbv2_groups* groups);
+int
+cbv2_groups_destroy(cbv2_groups* groups);
+size_t cbv2_group_topk_workspace_size(const cbv2_groups* groups, int32_t B, int32_t k, int32_t r);
+int
+cbv2_group_topk_rows(const cbv2_groups* groups, const float* scores, int64_t ld, int32_t B, int32_t k, int32_t r,
+                         void* workspace, size_t workspace_bytes, float* out_scores, int32_t* out_groups,
+                         int32_t* out_ids, float* out_chunk_scores, void* stream);
+size_t cbv2_search_grouped_workspace_size(const cbv2_index* index, const cbv2_groups* groups, int32_t B, int32_t lq,
+                                          int32_t k, int32_t r, int32_t scorer);
+int
+cbv2_search_grouped(cbv2_index* index, const cbv2_groups* groups, int32_t scorer, const void* Q, int32_t q_dtype,
+                        int32_t B, int32_t lq, int32_t k, int32_t r, void* workspace, size_t workspace_bytes,
+                        float* out_scores, int32_t* out_groups, int32_t* out_ids, float* out_chunk_scores,
+                        void* stream);
+
 /* cbv2_rerank — JinaColBERTRetriever.rerank (local_rag_complete.py:779-800)
  * without re-encoding: the C candidate docs of each query are GATHERED from
  * the HBM index by global id (cand int32 [B][C]; ids outside this shard or < 0
