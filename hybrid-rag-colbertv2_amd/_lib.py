@@ -24,10 +24,11 @@ ERR_EINVAL, ERR_EUNSUPPORTED, ERR_EHIP, ERR_ESTATE = -1, -2, -3, -4
 F32_SCORE, F32_SEARCH, F32_RERANK = 0, 1, 2
 (OPT_FUSED_TOPK, OPT_DYNAMIC_TAIL, OPT_BAND_DOC_MAJOR, OPT_BAND_LOWER_BOUND, OPT_TOPK_BMAX, OPT_BAND_FUSED,
  OPT_RESCORE_SPLIT, OPT_BAND_REUSE, OPT_BAND_BLOCK_SKIP, OPT_RESCORE_GRID, OPT_DENSE_DOCS, OPT_P1_COLLECT_FUSED,
- OPT_FOLD_KEYS, OPT_FILTER_PATH, OPT_FILTER_BATCH_CHUNK_DOCS, OPT_FILTER_BAND) = (1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12,
-                                                                                 13, 14, 15, 16)
+ OPT_FOLD_KEYS, OPT_FILTER_PATH, OPT_FILTER_BATCH_CHUNK_DOCS, OPT_FILTER_BAND,
+ OPT_GROUP_BAND) = (1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17)
 FILTER_AUTO, FILTER_SUBSET, FILTER_DENSE = 0, 1, 2
 FILTER_BAND_AUTO, FILTER_BAND_ON, FILTER_BAND_OFF = 0, 1, 2
+GROUP_BAND_AUTO, GROUP_BAND_ON, GROUP_BAND_OFF = 0, 1, 2
 
 _p, _i32, _i64, _sz = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_size_t
 _SIGS = {
@@ -80,6 +81,9 @@ _SIGS = {
     "cbv2_search_grouped_workspace_size": (_sz, [_p, _p, _i32, _i32, _i32, _i32, _i32]),
     "cbv2_search_grouped": (ctypes.c_int, [_p, _p, _i32, _p, _i32, _i32, _i32, _i32, _i32, _p, _sz, _p, _p, _p, _p,
                                            _p]),
+    "cbv2_search_grouped_f32_workspace_size": (_sz, [_p, _p, _i32, _i32, _i32, _i32, _i32]),
+    "cbv2_search_grouped_f32": (ctypes.c_int, [_p, _p, _p, _i32, _i32, _i32, _i32, _i32, _p, _sz, _p, _p, _p, _p, _p,
+                                               _p]),
     "cbv2_rerank": (ctypes.c_int, [_p, _p, _i32, _i32, _p, _i32, _i32, _p, _p, _p, _p]),
     "cbv2_rerank_workspace_bytes": (_sz, [_i32, _i32]),
     "cbv2_rerank_ws": (ctypes.c_int, [_p, _p, _i32, _i32, _p, _i32, _i32, _p, _sz, _p, _p, _p, _p]),

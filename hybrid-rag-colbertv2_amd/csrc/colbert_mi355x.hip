@@ -5907,6 +5907,7 @@ struct cbv2_index {
   std::vector<hipEvent_t> band_ev;
   int filter_path = 0;   // CBV2_OPT_FILTER_PATH (0: automatic, 1: subset where supported, 2: dense)
   int filter_band = 0;   // CBV2_OPT_FILTER_BAND (0: automatic, 1: the band where supported, 2: never)
+  int group_band = 0;    // CBV2_OPT_GROUP_BAND (0: automatic, 1: the band where supported, 2: never)
   int64_t filter_batch_chunk_docs = 0;   // CBV2_OPT_FILTER_BATCH_CHUNK_DOCS (0: automatic), read by cbv2_filter_batch_create
 };
 
@@ -7986,8 +7987,15 @@ __global__ __launch_bounds__(kGrpThreads) void group_reduce_kernel(const float* 
                                                                    const int32_t* __restrict__ order,
                                                                    const int32_t* __restrict__ offsets,
                                                                    int64_t members, int32_t groups,
-                                                                   uint32_t* __restrict__ keys) {
+                                                                   uint32_t* __restrict__ keys,
+                                                                   const int32_t* __restrict__ only_neg = nullptr) {
   const int lane = threadIdx.x & 63;
+  if (only_neg != nullptr) {   // a gated call: a workgroup none of whose rows is flagged has nothing to look up
+    bool any = false;
+    for (int b0 = blockIdx.y * kGrpRows; b0 < B; b0 += gridDim.y * kGrpRows)
+      for (int b = b0; b < b0 + kGrpRows && b < B; ++b) any = any || only_neg[b] < 0;
+    if (!any) return;          // block-uniform
+  }
   const int64_t tile0 = (int64_t)blockIdx.x * kGrpTile;
   int32_t id[kGrpPer], seg[kGrpPer];
   uint32_t link[kGrpPer];   // bit j: the position 2^j lanes below is in the same segment
@@ -8020,6 +8028,7 @@ __global__ __launch_bounds__(kGrpThreads) void group_reduce_kernel(const float* 
   for (int b0 = blockIdx.y * kGrpRows; b0 < B; b0 += gridDim.y * kGrpRows) {   // block-uniform
     const int b1 = b0 + kGrpRows < B ? b0 + kGrpRows : B;
     for (int b = b0; b < b1; ++b) {
+      if (only_neg != nullptr && only_neg[b] >= 0) continue;   // block-uniform: a gated call leaves this row alone
       const float* __restrict__ row = scores + (size_t)b * ld;
       uint32_t key[kGrpPer];
 #pragma unroll
@@ -8040,9 +8049,17 @@ __global__ __launch_bounds__(kGrpThreads) void group_reduce_kernel(const float* 
 }
 
 // keys -> the group-score row, in place (the two share the workspace block).
-__global__ __launch_bounds__(256) void group_rows_kernel(uint32_t* __restrict__ keys, int64_t total) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x)
-    keys[i] = __float_as_uint(u2f(keys[i]));
+// Key 0 is no score's key (f2u(-inf) = 0x007fffff is the smallest): it is what
+// the zeroing left in a group that nothing folded into -- only the band
+// reduce leaves such groups -- and becomes -inf, not u2f(0), a NaN.
+// only_neg (nullable): rows flagged < 0 only (row = i / groups).
+__global__ __launch_bounds__(256) void group_rows_kernel(uint32_t* __restrict__ keys, int64_t total, int32_t groups = 1,
+                                                         const int32_t* __restrict__ only_neg = nullptr) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    if (only_neg != nullptr && only_neg[i / groups] >= 0) continue;
+    const uint32_t key = keys[i];
+    keys[i] = __float_as_uint(key != 0u ? u2f(key) : neg_inf());
+  }
 }
 
 // Sorted insert into a descending list of kGrpMaxR keys (0 = empty slot);
@@ -8074,10 +8091,12 @@ __global__ __launch_bounds__(kGfThreads) void group_finish_kernel(const float* _
                                                                   int64_t id_base, const int32_t* __restrict__ sel_pos,
                                                                   int32_t* __restrict__ out_groups,
                                                                   int32_t* __restrict__ out_ids,
-                                                                  float* __restrict__ out_cs) {
+                                                                  float* __restrict__ out_cs,
+                                                                  const int32_t* __restrict__ only_neg = nullptr) {
   __shared__ uint64_t s_best[kGfThreads / 64];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   for (int b = blockIdx.y; b < B; b += gridDim.y) {
+    if (only_neg != nullptr && only_neg[b] >= 0) continue;   // block-uniform
     for (int j = blockIdx.x; j < k; j += gridDim.x) {   // (b, j): block-uniform
       const size_t slot = (size_t)b * k + j;
       const int32_t pos = sel_pos[slot];
@@ -8222,7 +8241,39 @@ int check_group_args(const cbv2_groups* g, int32_t B, int32_t k, int32_t r, cons
 
 int group_select_impl(const cbv2_groups* g, const float* scores, int64_t ld, int32_t B, int32_t k, int32_t r,
                       const GroupWs& w, float* out_scores, int32_t* out_groups, int32_t* out_ids,
-                      float* out_chunk_scores, hipStream_t st) {
+                      float* out_chunk_scores, hipStream_t st, const int32_t* only_neg = nullptr) {
+  if (only_neg != nullptr) {
+    // The gated form (the grouped faithful band's recomputation of the rows
+    // flagged < 0; G' > k there): every launch skips the other rows, whose
+    // outputs stay as they are.  Their keys are zeroed with the rest -- the
+    // band is done with them by now.  The row top-k is topk_rows_kernel /
+    // topk_multi, the gated selections topk_impl's other routes agree with bit
+    // for bit (search_filtered_f32_impl's overflow rows take them too).
+    const int64_t total = (int64_t)B * g->groups;
+    CBV2_HIP(hipMemsetAsync(w.keys, 0, (size_t)total * sizeof(uint32_t), st));
+    const int64_t tiles = (g->members + kGrpTile - 1) / kGrpTile;
+    const int64_t gy = std::min<int64_t>((B + kGrpRows - 1) / kGrpRows, 65535);
+    hipLaunchKernelGGL(group_reduce_kernel, dim3((unsigned)tiles, (unsigned)gy), dim3(kGrpThreads), 0, st, scores, ld,
+                       B, g->order, g->offsets, g->members, g->groups, w.keys, only_neg);
+    int rc = launch_check("group_reduce_kernel");
+    if (rc) return rc;
+    hipLaunchKernelGGL(group_rows_kernel, dim3((unsigned)std::min<int64_t>((total + 255) / 256, 65535)), dim3(256), 0,
+                       st, w.keys, total, g->groups, only_neg);
+    if ((rc = launch_check("group_rows_kernel"))) return rc;
+    if (k > kTopkMax) {
+      if ((rc = topk_multi((const float*)w.keys, B, g->groups, g->groups, k, 0, nullptr, 0, out_scores, w.pos, nullptr,
+                           st, only_neg)))
+        return rc;
+    } else {
+      hipLaunchKernelGGL(topk_rows_kernel, dim3((unsigned)B), dim3(kTkThreads), 0, st, (const float*)w.keys,
+                         (int64_t)g->groups, (int64_t)g->groups, k, (int64_t)0, out_scores, w.pos, only_neg, Mirror());
+      if ((rc = launch_check("topk_rows_kernel"))) return rc;
+    }
+    hipLaunchKernelGGL(group_finish_kernel, dim3((unsigned)std::min<int32_t>(k, 1 << 20), (unsigned)std::min(B, 65535)),
+                       dim3(kGfThreads), 0, st, scores, ld, B, k, r, g->order, g->offsets, g->labels, g->groups,
+                       g->id_base, w.pos, out_groups, out_ids, out_chunk_scores, only_neg);
+    return launch_check("group_finish_kernel");
+  }
   if (g->groups == 0 || g->n == 0) {   // padding only
     const int64_t slots = (int64_t)B * k;
     const int64_t gx = std::min<int64_t>((slots * r + 255) / 256, 65535);
@@ -8275,6 +8326,418 @@ size_t group_search_layout(const cbv2_index* ix, const cbv2_groups* g, int32_t B
     w->f32 = base ? base + off : nullptr;
     off += f32_ws_layout(ix, CBV2_F32_SCORE, B, lq, 0, nullptr, &f);
   }
+  return off;
+}
+
+// ---------------------------------------------------------------------------
+// Grouped faithful search with a certified band (cbv2_search_grouped_f32;
+// cbv2_search_grouped on a faithful index with f32 queries).  Same bits as the
+// full faithful scan + group_select_impl, far fewer faithful pairs.  With T
+// the bf16 scan of hi, S the faithful score, beta(q) >= |T - S| for every
+// chunk (the query split's bound), per row:
+//  1. split, bf16 scan into T [B][n];
+//  2. group_select_impl on T with r = 1: the k best groups by T and their
+//     T-leaders -- k chunks of k distinct groups;
+//  3. lb = the minimum faithful score of those k chunks: k distinct groups
+//     score at least lb, so the k-th group score is >= lb;
+//  4. the global band: every member chunk with T >= lb - beta.  A chunk outside
+//     has S <= T + beta < lb and leads no top-k group; a chunk that ties with a
+//     top-k group's leader has S >= lb and is inside.  lb = -inf (fewer than k
+//     finite groups) makes the band every member;
+//  5. the band's faithful scores;
+//  6. keys[b][segment] = max over the band (32-bit atomic max on the order-
+//     preserving bits; key 0 = no band chunk = -inf), then the row top-k over
+//     [B][G'].  A top-k group's best chunk is in the band, so its key is its
+//     score; any other group's key is at most its score: scores, order and the
+//     tie rule (group index ascending) are the full path's;
+//  7. per selected group g: its top-r chunks by T (group_finish_kernel on T),
+//     their faithful scores, s_g = their minimum (padding ids score -inf).  r
+//     chunks of g score >= s_g, so a chunk of g with T < s_g - beta has S < s_g
+//     and is not among g's best r; a chunk tying with the r-th has S >= s_g and
+//     is kept.  A group of fewer than r finite chunks has s_g = -inf: its whole
+//     segment is collected;
+//  8. those chunks' faithful scores, and per (row, slot) the best r by
+//     rank_key(score, chunk id).  The group's best chunk is among them (its S is
+//     the group score >= s_g), scored by the same function on the same operands
+//     as in step 5 (faithful_doc_split: a pair's bits do not depend on the
+//     launch, the grid or the wave count), hence out_chunk_scores[b][j][0] has
+//     out_scores[b][j]'s bits;
+//  9. a row whose list of step 4 or of step 7 exceeds cap: status -1, the full
+//     faithful scan into its T row and the gated selection; the other rows'
+//     workgroups exit at once.
+// Every replay re-initialises what it counts in: the split resets count and
+// lb, memsets reset the second count and the keys, the finish writes status.
+// ---------------------------------------------------------------------------
+constexpr int kGbThreads = 256;
+constexpr int kGbUnroll = 8;                        // loads in flight per thread
+constexpr int kGbTile = kGbThreads * kGbUnroll;     // order positions per tile of a collect
+
+// The collects' lists: (id, tag) pairs of the lanes with `take` set, gathered
+// in LDS (one LDS atomic per wave with a hit), flushed with one global atomic
+// per workgroup; past kBandLds entries straight to the row's global list.
+// Entries at or past cap are dropped: count[b] > cap marks the overflow.
+__device__ __forceinline__ void group_list_offer(bool take, int32_t id, int32_t tag, int32_t* s_id, int32_t* s_tag,
+                                                 int* s_n, int32_t* count_b, int cap, int32_t* crow, int32_t* trow,
+                                                 int lane) {
+  const uint64_t mask = __ballot(take);
+  if (mask == 0) return;
+  int base = 0;
+  if (lane == 0) base = atomicAdd(s_n, __popcll(mask));
+  base = __shfl(base, 0);
+  const int pos = base + __popcll(mask & ((1ull << lane) - 1ull));
+  if (take) {
+    if (pos < kBandLds) {
+      s_id[pos] = id;
+      s_tag[pos] = tag;
+    } else {
+      const int gp = atomicAdd(count_b, 1);
+      if (gp >= 0 && gp < cap) {
+        crow[gp] = id;
+        trow[gp] = tag;
+      }
+    }
+  }
+}
+__device__ __forceinline__ void group_list_flush(const int32_t* s_id, const int32_t* s_tag, const int* s_n, int* s_base,
+                                                 int32_t* count_b, int cap, int32_t* crow, int32_t* trow) {
+  __syncthreads();
+  const int nl = *s_n < kBandLds ? *s_n : kBandLds;
+  if (threadIdx.x == 0) *s_base = nl > 0 ? atomicAdd(count_b, nl) : 0;
+  __syncthreads();
+  const int b0 = *s_base;
+  for (int t = threadIdx.x; t < nl; t += blockDim.x)
+    if (b0 >= 0 && b0 + t < cap) {
+      crow[b0 + t] = s_id[t];
+      trow[b0 + t] = s_tag[t];
+    }
+}
+
+// Step 4.  Walks ORDER positions (grid-stride tiles, grid.y = rows): chunks in
+// no group are never touched; a hit's segment is found by a binary search of
+// offsets (hits are few).  cand[b][.] = global chunk id, seg[b][.] = segment.
+__global__ __launch_bounds__(kGbThreads) void group_band_collect_kernel(
+    const float* __restrict__ T, int64_t ld, const int32_t* __restrict__ order, const int32_t* __restrict__ offsets,
+    int64_t members, int32_t groups, int64_t id_base, const float* __restrict__ beta, const uint32_t* __restrict__ lbu,
+    int cap, int32_t* __restrict__ cand, int32_t* __restrict__ seg, int32_t* __restrict__ count) {
+  __shared__ int32_t s_id[kBandLds], s_tag[kBandLds];
+  __shared__ int s_n, s_base;
+  const int b = blockIdx.y, lane = threadIdx.x & 63;
+  if (threadIdx.x == 0) s_n = 0;
+  __syncthreads();
+  const float thr = u2f(lbu[b]) - beta[b];
+  const float* __restrict__ row = T + (size_t)b * ld;
+  int32_t* crow = cand + (size_t)b * cap;
+  int32_t* trow = seg + (size_t)b * cap;
+  const int64_t step = (int64_t)gridDim.x * kGbTile;
+  for (int64_t p0 = (int64_t)blockIdx.x * kGbTile; p0 < members; p0 += step) {   // block-uniform
+    int32_t id[kGbUnroll];
+    float v[kGbUnroll];
+#pragma unroll
+    for (int u = 0; u < kGbUnroll; ++u) {
+      const int64_t p = p0 + (int64_t)u * kGbThreads + threadIdx.x;
+      id[u] = p < members ? order[p] : -1;
+    }
+#pragma unroll
+    for (int u = 0; u < kGbUnroll; ++u) v[u] = id[u] >= 0 ? row[id[u]] : 0.0f;
+#pragma unroll
+    for (int u = 0; u < kGbUnroll; ++u) {
+      const bool take = id[u] >= 0 && v[u] >= thr;
+      int32_t s = 0;
+      if (take) {
+        const int64_t p = p0 + (int64_t)u * kGbThreads + threadIdx.x;
+        int32_t lo = 0, hi = groups;   // offsets[lo] <= p < offsets[hi]
+        while (hi - lo > 1) {
+          const int32_t mid = lo + ((hi - lo) >> 1);
+          if ((int64_t)offsets[mid] <= p) lo = mid; else hi = mid;
+        }
+        s = lo;
+      }
+      group_list_offer(take, (int32_t)(id_base + id[u]), s, s_id, s_tag, &s_n, count + b, cap, crow, trow, lane);
+    }
+  }
+  group_list_flush(s_id, s_tag, &s_n, &s_base, count + b, cap, crow, trow);
+}
+
+// Step 6.  keys[b][seg] = max of the band's faithful scores (order-preserving
+// bits; the keys were zeroed).  Rows whose band overflowed are left to step 9.
+__global__ __launch_bounds__(256) void group_band_reduce_kernel(const float* __restrict__ F,
+                                                                const int32_t* __restrict__ seg,
+                                                                const int32_t* __restrict__ count, int cap,
+                                                                int32_t groups, uint32_t* __restrict__ keys) {
+  const int b = blockIdx.y;
+  const int cnt = count[b];
+  if (cnt > cap) return;   // block-uniform
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < cnt; i += gridDim.x * blockDim.x) {
+    const int32_t s = seg[(size_t)b * cap + i];
+    if (s >= 0 && s < groups) atomicMax(keys + (size_t)b * groups + s, f2u(F[(size_t)b * cap + i]));
+  }
+}
+
+// Step 7.  grid (tiles, k, B): the segment of selected slot j is walked in
+// fixed tiles of kGbTile order positions by gridDim.x workgroups (tile-stride),
+// so one group of half the corpus beside singletons is the work of many
+// workgroups, not one.  lead [B][k][r]: the faithful scores of the slot's top-r
+// chunks by T; s_g = their minimum.  cand[b][.] = global id, slot[b][.] = j.
+__global__ __launch_bounds__(kGbThreads) void group_segment_collect_kernel(
+    const float* __restrict__ T, int64_t ld, const int32_t* __restrict__ order, const int32_t* __restrict__ offsets,
+    int32_t groups, int64_t id_base, const int32_t* __restrict__ sel_pos, int k, int r, const float* __restrict__ lead,
+    const float* __restrict__ beta, const int32_t* __restrict__ count1, int cap, int32_t* __restrict__ cand,
+    int32_t* __restrict__ slot, int32_t* __restrict__ count) {
+  __shared__ int32_t s_id[kBandLds], s_tag[kBandLds];
+  __shared__ int s_n, s_base;
+  const int b = blockIdx.z, j = blockIdx.y, lane = threadIdx.x & 63;
+  if (count1[b] > cap) return;   // block-uniform: the global band overflowed, step 9 recomputes the row
+  const int32_t pos = sel_pos[(size_t)b * k + j];
+  if (pos < 0 || pos >= groups) return;
+  const int64_t beg = offsets[pos], end = offsets[pos + 1];
+  if (beg + (int64_t)blockIdx.x * kGbTile >= end) return;
+  if (threadIdx.x == 0) s_n = 0;
+  __syncthreads();
+  float sg = lead[((size_t)b * k + j) * r];
+  for (int t = 1; t < r; ++t) sg = fminf(sg, lead[((size_t)b * k + j) * r + t]);
+  const float thr = sg - beta[b];
+  const float* __restrict__ row = T + (size_t)b * ld;
+  int32_t* crow = cand + (size_t)b * cap;
+  int32_t* trow = slot + (size_t)b * cap;
+  const int64_t step = (int64_t)gridDim.x * kGbTile;
+  for (int64_t p0 = beg + (int64_t)blockIdx.x * kGbTile; p0 < end; p0 += step) {   // block-uniform
+    int32_t id[kGbUnroll];
+    float v[kGbUnroll];
+#pragma unroll
+    for (int u = 0; u < kGbUnroll; ++u) {
+      const int64_t p = p0 + (int64_t)u * kGbThreads + threadIdx.x;
+      id[u] = p < end ? order[p] : -1;
+    }
+#pragma unroll
+    for (int u = 0; u < kGbUnroll; ++u) v[u] = id[u] >= 0 ? row[id[u]] : 0.0f;
+#pragma unroll
+    for (int u = 0; u < kGbUnroll; ++u)
+      group_list_offer(id[u] >= 0 && v[u] >= thr, (int32_t)(id_base + id[u]), j, s_id, s_tag, &s_n, count + b, cap,
+                       crow, trow, lane);
+  }
+  group_list_flush(s_id, s_tag, &s_n, &s_base, count + b, cap, crow, trow);
+}
+
+// Step 8.  One workgroup per (row b, slot j): the best r of the row's list
+// entries tagged j, by rank_key(faithful score, local chunk id) -- every
+// thread keeps its best kGrpMaxR, then r rounds pick the largest head, as
+// group_finish_kernel -- and the padding (-1 / -inf past the group's size).
+// Slot 0's workgroup writes the row's status: the global band's size, or -1
+// when either list overflowed (the row's outputs are then step 9's).
+__global__ __launch_bounds__(kGbThreads) void group_band_finish_kernel(
+    const float* __restrict__ F, const int32_t* __restrict__ cand, const int32_t* __restrict__ slot,
+    const int32_t* __restrict__ count1, const int32_t* __restrict__ count2, int cap, int k, int r, int64_t id_base,
+    int32_t* __restrict__ out_ids, float* __restrict__ out_cs, int32_t* __restrict__ status) {
+  __shared__ uint64_t s_best[kGbThreads / 64];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int b = blockIdx.y, j = blockIdx.x;
+  const int c1 = count1[b], c2 = count2[b];
+  const bool over = c1 > cap || c2 > cap;   // block-uniform
+  if (j == 0 && tid == 0) status[b] = over ? -1 : c1;
+  if (over) return;
+  uint64_t l[kGrpMaxR];
+#pragma unroll
+  for (int i = 0; i < kGrpMaxR; ++i) l[i] = 0ull;
+  const size_t row = (size_t)b * cap;
+  for (int i = tid; i < c2; i += kGbThreads)
+    if (slot[row + i] == j)
+      group_best_insert(l, rank_key(F[row + i], (uint32_t)((int64_t)cand[row + i] - id_base)));
+  const size_t o = ((size_t)b * k + j) * r;
+  for (int t = 0; t < r; ++t) {   // block-uniform
+    uint64_t m = l[0];
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+      const uint64_t x = __shfl_xor((unsigned long long)m, d);
+      m = x > m ? x : m;
+    }
+    if (lane == 0) s_best[wave] = m;
+    __syncthreads();
+    m = s_best[0];
+#pragma unroll
+    for (int w = 1; w < kGbThreads / 64; ++w) m = s_best[w] > m ? s_best[w] : m;
+    __syncthreads();   // every wave has read s_best before the next round writes it
+    if (m != 0ull && l[0] == m) {   // the owner pops its head
+#pragma unroll
+      for (int i = 0; i + 1 < kGrpMaxR; ++i) l[i] = l[i + 1];
+      l[kGrpMaxR - 1] = 0ull;
+    }
+    if (tid == 0) {
+      out_ids[o + t] = m != 0ull ? (int32_t)(id_base + (int64_t)(~(uint32_t)m)) : -1;
+      out_cs[o + t] = m != 0ull ? u2f((uint32_t)(m >> 32)) : neg_inf();
+    }
+  }
+}
+
+// The band's part of the workspace, behind group_search_layout's blocks.
+struct GroupBandWs {
+  int32_t* status = nullptr;   // [B] (cbv2_search_grouped keeps it here)
+  uint32_t* lb = nullptr;      // [B] order-preserving bits of the rows' lower bound
+  int32_t* count = nullptr;    // [B] the global band's size
+  int32_t* count2 = nullptr;   // [B] the per-group bands' total size
+  int32_t* cand = nullptr;     // [B][cap] global chunk ids (step 4, then step 7)
+  int32_t* tag = nullptr;      // [B][cap] segment (step 4) / slot (step 7)
+  float* F = nullptr;          // [B][cap] their faithful scores
+  float* t_s = nullptr;        // [B][k] step 2's group scores by T
+  int32_t* t_g = nullptr;      // [B][k] and group indices (unused beyond the call)
+  int32_t* t_i = nullptr;      // [B][k] the T-leaders' global ids
+  float* t_c = nullptr;        // [B][k] their T, then their faithful scores
+  int32_t* lead_i = nullptr;   // [B][k][r] step 7: each selected group's top-r chunks by T
+  float* lead_T = nullptr;     // [B][k][r] their T
+  float* lead_F = nullptr;     // [B][k][r] their faithful scores
+};
+size_t group_band_layout(int32_t B, int32_t k, int32_t r, int32_t cap, uint8_t* base, GroupBandWs* w) {
+  size_t off = 0;
+  auto take = [&](size_t bytes) -> uint8_t* {
+    uint8_t* p = base ? base + off : nullptr;
+    off += (bytes + 255) & ~(size_t)255;
+    return p;
+  };
+  const size_t b4 = (size_t)B * 4, bc = (size_t)B * cap * 4, bk = (size_t)B * k * 4, bkr = bk * r;
+  w->status = (int32_t*)take(b4);
+  w->lb = (uint32_t*)take(b4);
+  w->count = (int32_t*)take(b4);
+  w->count2 = (int32_t*)take(b4);
+  w->cand = (int32_t*)take(bc);
+  w->tag = (int32_t*)take(bc);
+  w->F = (float*)take(bc);
+  w->t_s = (float*)take(bk);
+  w->t_g = (int32_t*)take(bk);
+  w->t_i = (int32_t*)take(bk);
+  w->t_c = (float*)take(bk);
+  w->lead_i = (int32_t*)take(bkr);
+  w->lead_T = (float*)take(bkr);
+  w->lead_F = (float*)take(bkr);
+  return off;
+}
+
+// CBV2_OPT_GROUP_BAND.  The band needs something to bound (G' > k), a k the
+// band lists can hold, and the split rescoring (its gate and lb_min).
+// Automatic: the band when the faithful pairs it can save pay for its extra
+// launches, filter_f32_mode's form,
+//     B * (n - 4 k r)  >=  kGroupBandMinSavedPairs,
+// and its band is expected to fit:  members * k / G'  <=  cap.
+// Left: the full path scores every chunk of the index, member or not (a
+// grouping of 2,000 of 1M chunks: 10.7 ms at B = 1, as with all of them), hence
+// n; the band rescores the k leaders, a global band of at least k, the k r
+// chunks of step 7 and per-group bands of at least k r: at most 4 k r pairs
+// that are certain.  Right: its ~15 extra launches in faithful pairs.
+// Measured with k = 100, `ten` grouping, band vs full, medians of 5
+// (tools/group_band_sweep.py --docs n; profiles/group_band_sweep.jsonl): the
+// full path wins at B=1 n=2,000 / 5,000 / 10,000 (left side 1,600 .. 9,600:
+// 0.155 vs 0.082, 0.172 vs 0.110, 0.200 vs 0.173 ms), at B=1 n=20,000 r=3
+// (18,800: 0.284 vs 0.278) and at B=16 n=2,000 (25,600: 0.363 vs 0.351; r=3
+// 12,800: 0.44 vs 0.35); the band wins at B=1 n=50,000 (49,600: 0.429 vs 0.621;
+// r=3 48,800: 0.437 vs 0.604), B=16 n=5,000 (73,600: 0.40 vs 0.75) and at every
+// larger point (1M chunks: 4.74 vs 10.9 ms at B=1, 11.7 vs 170 at B=16, 144 vs
+// 2,697 at B=256).  B=1 n=20,000 r=1 (19,600) is a tie (0.273 vs 0.282).  The
+// threshold sits between 25,600 and 48,800.
+// The fit: with exchangeable scores the chunks at or above the k-th group score
+// number about members k / G'.  Measured bands at 1M chunks: `ten` (estimate
+// 1,000) 864 .. 1,119, `half` (2,000) 1,655 .. 2,061; `zipf` (412 groups:
+// 242,718) overflowed 16,384 in every row and then costs the full path plus
+// 8 % (15.95 vs 10.77 ms at B=1; 182.7 vs 168.3 at B=16).  No grouping between
+// those was measured; no other k either.  Long documents keep the constants,
+// unmeasured there.
+constexpr int64_t kGroupBandMinSavedPairs = 40000;
+bool group_band_wanted(const cbv2_index* ix, const cbv2_groups* g, int32_t B, int32_t k, int32_t r) {
+  if (ix->n == 0 || g->groups <= k || k > kBandCapMax || !ix->rescore_split || ix->group_band == 2) return false;
+  if (ix->group_band == 1) return true;
+  return (int64_t)B * (ix->n - 4LL * k * r) >= kGroupBandMinSavedPairs;
+}
+// (cap in [k, kBandCapMax] has been checked where the band is wanted)
+bool group_band_taken(const cbv2_index* ix, const cbv2_groups* g, int32_t B, int32_t k, int32_t r, int32_t cap) {
+  if (!group_band_wanted(ix, g, B, k, r) || (int64_t)k * r > cap) return false;
+  return ix->group_band == 1 || g->members * k / g->groups <= cap;
+}
+
+// The faithful grouped search.  band: group_band_taken.  out_status nullable
+// on the full path only (cbv2_search_grouped reports none).
+int search_grouped_f32_impl(cbv2_index* ix, const cbv2_groups* g, const float* Q, int32_t B, int32_t lq, int32_t k,
+                            int32_t r, int32_t cap, bool band, GroupSearchWs& w, GroupBandWs& bw, float* out_scores,
+                            int32_t* out_groups, int32_t* out_ids, float* out_chunk_scores, int32_t* out_status,
+                            hipStream_t st) {
+  int rc;
+  F32Ws f;
+  f32_ws_layout(ix, CBV2_F32_SCORE, B, lq, 0, w.f32, &f);
+  if (g->groups == 0 || ix->n == 0) {   // padding only, no scan
+    if (out_status != nullptr) CBV2_HIP(hipMemsetAsync(out_status, 0, (size_t)B * sizeof(int32_t), st));
+    return group_select_impl(g, w.S, ix->n, B, k, r, w.sel, out_scores, out_groups, out_ids, out_chunk_scores, st);
+  }
+  if (!band) {   // cbv2_score_f32's full faithful scan, then the selection
+    if (out_status != nullptr) CBV2_HIP(hipMemsetAsync(out_status, 0xff, (size_t)B * sizeof(int32_t), st));
+    if ((rc = split_queries(ix, Q, B, lq, &f, st))) return rc;
+    if ((rc = launch_rescore(ix, &f, B, lq, nullptr, nullptr, ix->n, 0, w.S, ix->n, st))) return rc;
+    return group_select_impl(g, w.S, ix->n, B, k, r, w.sel, out_scores, out_groups, out_ids, out_chunk_scores, st);
+  }
+  const int32_t G = g->groups;
+  const int cus = cu_count(ix->device);
+  // 1. the split (it resets count = 0 and lb), the bf16 scan of hi into T
+  f.count = bw.count;
+  f.lb = reinterpret_cast<float*>(bw.lb);
+  if ((rc = split_queries(ix, Q, B, lq, &f, st, 0))) return rc;
+  CBV2_HIP(hipMemsetAsync(bw.count2, 0, (size_t)B * sizeof(int32_t), st));
+  float* T = w.S;
+  if ((rc = scan_maxsim_timed(ix, f.qhi, B, lq, T, ix->n, st, w.ctr))) return rc;
+  // 2. the k best groups by T and their T-leaders (G' > k: no padding)
+  if ((rc = group_select_impl(g, T, ix->n, B, k, 1, w.sel, bw.t_s, bw.t_g, bw.t_i, bw.t_c, st))) return rc;
+  // 3. lb = the minimum faithful score of those k chunks
+  if ((rc = launch_rescore(ix, &f, B, lq, bw.t_i, nullptr, k, k, bw.t_c, k, st, nullptr, 0, bw.lb))) return rc;
+  // 4. the global band over the members
+  {
+    int64_t splits = (8LL * cus + B - 1) / B;    // ~8 workgroups per CU
+    splits = std::max<int64_t>(1, std::min<int64_t>(splits, (g->members + kGbTile - 1) / kGbTile));
+    hipLaunchKernelGGL(group_band_collect_kernel, dim3((unsigned)splits, (unsigned)B), dim3(kGbThreads), 0, st, T,
+                       ix->n, g->order, g->offsets, g->members, G, g->id_base, f.beta, bw.lb, cap, bw.cand, bw.tag,
+                       bw.count);
+    if ((rc = launch_check("group_band_collect_kernel"))) return rc;
+  }
+  // 5. its faithful scores
+  if ((rc = launch_rescore(ix, &f, B, lq, bw.cand, bw.count, cap, cap, bw.F, cap, st))) return rc;
+  // 6. the band's group keys, the group rows, their top-k
+  const int64_t total = (int64_t)B * G;
+  CBV2_HIP(hipMemsetAsync(w.sel.keys, 0, (size_t)total * sizeof(uint32_t), st));
+  hipLaunchKernelGGL(group_band_reduce_kernel, dim3((unsigned)std::min<int64_t>((cap + 255) / 256, 16), (unsigned)B),
+                     dim3(256), 0, st, bw.F, bw.tag, bw.count, cap, G, w.sel.keys);
+  if ((rc = launch_check("group_band_reduce_kernel"))) return rc;
+  hipLaunchKernelGGL(group_rows_kernel, dim3((unsigned)std::min<int64_t>((total + 255) / 256, 65535)), dim3(256), 0, st,
+                     w.sel.keys, total, G, (const int32_t*)nullptr);
+  if ((rc = launch_check("group_rows_kernel"))) return rc;
+  if ((rc = topk_impl((const float*)w.sel.keys, B, G, G, k, 0, w.sel.tk, w.sel.tk_bytes, out_scores, w.sel.pos, st,
+                      g->device)))
+    return rc;
+  // 7. each selected group's top-r chunks by T, their faithful scores, the per-group bands
+  const dim3 gfin((unsigned)std::min<int32_t>(k, 1 << 20), (unsigned)std::min(B, 65535));
+  hipLaunchKernelGGL(group_finish_kernel, gfin, dim3(kGfThreads), 0, st, T, ix->n, B, k, r, g->order, g->offsets,
+                     g->labels, G, g->id_base, w.sel.pos, out_groups, bw.lead_i, bw.lead_T, (const int32_t*)nullptr);
+  if ((rc = launch_check("group_finish_kernel"))) return rc;
+  const int64_t kr = (int64_t)k * r;
+  if ((rc = launch_rescore(ix, &f, B, lq, bw.lead_i, nullptr, kr, kr, bw.lead_F, kr, st))) return rc;
+  {
+    const int64_t tiles = (g->largest + kGbTile - 1) / kGbTile;
+    const int64_t per = std::max<int64_t>(1, 16LL * cus / ((int64_t)B * k));   // workgroups per selected segment
+    const dim3 grid((unsigned)std::max<int64_t>(1, std::min(tiles, per)), (unsigned)k, (unsigned)B);
+    hipLaunchKernelGGL(group_segment_collect_kernel, grid, dim3(kGbThreads), 0, st, T, ix->n, g->order, g->offsets, G,
+                       g->id_base, w.sel.pos, k, r, bw.lead_F, f.beta, bw.count, cap, bw.cand, bw.tag, bw.count2);
+    if ((rc = launch_check("group_segment_collect_kernel"))) return rc;
+  }
+  // 8. their faithful scores, each slot's best r, the rows' status
+  if ((rc = launch_rescore(ix, &f, B, lq, bw.cand, bw.count2, cap, cap, bw.F, cap, st))) return rc;
+  hipLaunchKernelGGL(group_band_finish_kernel, dim3((unsigned)k, (unsigned)B), dim3(kGbThreads), 0, st, bw.F, bw.cand,
+                     bw.tag, bw.count, bw.count2, cap, k, r, g->id_base, out_ids, out_chunk_scores, out_status);
+  if ((rc = launch_check("group_band_finish_kernel"))) return rc;
+  // 9. rows with status -1: the full faithful scan into their T rows and the
+  //    gated selection (every other row's workgroups exit at once)
+  if ((rc = launch_rescore(ix, &f, B, lq, nullptr, nullptr, ix->n, 0, T, ix->n, st, out_status))) return rc;
+  return group_select_impl(g, T, ix->n, B, k, r, w.sel, out_scores, out_groups, out_ids, out_chunk_scores, st,
+                           out_status);
+}
+
+// Where the band's blocks start in a grouped search's workspace, and the
+// whole size: cap == 0 lays out no band.
+size_t group_search_f32_layout(const cbv2_index* ix, const cbv2_groups* g, int32_t B, int32_t lq, int32_t k, int32_t r,
+                               int32_t cap, uint8_t* base, GroupSearchWs* w, GroupBandWs* bw) {
+  size_t off = group_search_layout(ix, g, B, lq, k, CBV2_SCORER_MAXSIM, base, w);
+  if (cap > 0) off += group_band_layout(B, k, r, cap, base ? base + off : nullptr, bw);
   return off;
 }
 }  // namespace
@@ -8957,7 +9420,54 @@ size_t cbv2_search_grouped_workspace_size(const cbv2_index* ix, const cbv2_group
                                           int32_t r, int32_t scorer) {
   if (!ix || !g || B < 1 || lq < 1 || k < 1 || r < 1 || r > kGrpMaxR) return 0;
   GroupSearchWs w;
+  if (ix->resid != nullptr && scorer == CBV2_SCORER_MAXSIM && lq <= kLqMax) {   // f32 queries may take the band
+    const int32_t cap = std::max<int32_t>(CBV2_RETRIEVE_BAND_CAP, k);
+    GroupBandWs bw;
+    return group_search_f32_layout(ix, g, B, lq, k, r, group_band_taken(ix, g, B, k, r, cap) ? cap : 0, nullptr, &w,
+                                   &bw);
+  }
   return group_search_layout(ix, g, B, lq, k, scorer, nullptr, &w);
+}
+
+size_t cbv2_search_grouped_f32_workspace_size(const cbv2_index* ix, const cbv2_groups* g, int32_t B, int32_t lq,
+                                              int32_t k, int32_t r, int32_t cap) {
+  if (!ix || !g || B < 1 || B > 65535 || lq < 1 || lq > kLqMax || k < 1 || r < 1 || r > kGrpMaxR) return 0;
+  if (ix->resid == nullptr) return 0;
+  const bool wanted = group_band_wanted(ix, g, B, k, r);
+  if (wanted && (cap < k || cap > kBandCapMax)) return 0;
+  GroupSearchWs w;
+  GroupBandWs bw;
+  return group_search_f32_layout(ix, g, B, lq, k, r, group_band_taken(ix, g, B, k, r, cap) ? cap : 0, nullptr, &w,
+                                 &bw);
+}
+
+int cbv2_search_grouped_f32(cbv2_index* ix, const cbv2_groups* g, const float* Q, int32_t B, int32_t lq, int32_t k,
+                            int32_t r, int32_t cap, void* ws, size_t ws_bytes, float* out_scores, int32_t* out_groups,
+                            int32_t* out_ids, float* out_chunk_scores, int32_t* out_status, void* stream) {
+  CBV2_REQUIRE(g != nullptr, "null groups handle");
+  CBV2_REQUIRE(ix != nullptr, "null index");
+  if (ix->resid == nullptr) return fail(CBV2_ESTATE, "index has no fp32 residual (cbv2_index_attach_residual)");
+  CBV2_REQUIRE(Q != nullptr && aligned16(Q), "query pointer must be non-null and 16-byte aligned");
+  CBV2_REQUIRE(B >= 1 && B <= 65535, "B must be in [1, 65535] (got %d)", B);
+  CBV2_REQUIRE(lq >= 1 && lq <= kLqMax, "lq must be in [1, %d] (got %d)", kLqMax, lq);
+  CBV2_REQUIRE(g->n == ix->n && g->id_base == ix->id_base && g->device == ix->device,
+               "the groups were created for another index (n %lld / %lld, id_base %lld / %lld, device %d / %d)",
+               (long long)g->n, (long long)ix->n, (long long)g->id_base, (long long)ix->id_base, g->device, ix->device);
+  if (int rc = check_group_args(g, B, k, r, out_scores, out_groups, out_ids, out_chunk_scores)) return rc;
+  CBV2_REQUIRE(out_status != nullptr, "null out_status");
+  const bool wanted = group_band_wanted(ix, g, B, k, r);
+  if (wanted) CBV2_REQUIRE(cap >= k && cap <= kBandCapMax, "cap must be in [k, %d] (got %d, k %d)", kBandCapMax, cap, k);
+  const bool band = group_band_taken(ix, g, B, k, r, cap);
+  GroupSearchWs w;
+  GroupBandWs bw;
+  const size_t need = group_search_f32_layout(ix, g, B, lq, k, r, band ? cap : 0, nullptr, &w, &bw);
+  CBV2_REQUIRE(ws != nullptr && ws_bytes >= need && aligned16(ws), "workspace too small or misaligned (%zu < %zu)",
+               ws_bytes, need);
+  group_search_f32_layout(ix, g, B, lq, k, r, band ? cap : 0, (uint8_t*)ws, &w, &bw);
+  DeviceGuard dg(ix->device);
+  if (!dg.ok) return fail(CBV2_EHIP, "cannot select device %d", ix->device);
+  return search_grouped_f32_impl(ix, g, Q, B, lq, k, r, cap, band, w, bw, out_scores, out_groups, out_ids,
+                                 out_chunk_scores, out_status, (hipStream_t)stream);
 }
 
 int cbv2_search_grouped(cbv2_index* ix, const cbv2_groups* g, int32_t scorer, const void* Q, int32_t q_dtype, int32_t B,
@@ -8979,24 +9489,24 @@ int cbv2_search_grouped(cbv2_index* ix, const cbv2_groups* g, int32_t scorer, co
                (long long)g->n, (long long)ix->n, (long long)g->id_base, (long long)ix->id_base, g->device, ix->device);
   if (int rc = check_group_args(g, B, k, r, out_scores, out_groups, out_ids, out_chunk_scores)) return rc;
   GroupSearchWs w;
-  const size_t need = group_search_layout(ix, g, B, lq, k, scorer, nullptr, &w);
+  GroupBandWs bw;
+  // (the size function's layout: on an index with a residual it covers the band of f32 queries)
+  const size_t need = cbv2_search_grouped_workspace_size(ix, g, B, lq, k, r, scorer);
   CBV2_REQUIRE(ws != nullptr && ws_bytes >= need && aligned16(ws), "workspace too small or misaligned (%zu < %zu)",
                ws_bytes, need);
-  group_search_layout(ix, g, B, lq, k, scorer, (uint8_t*)ws, &w);
   DeviceGuard dg(ix->device);
   if (!dg.ok) return fail(CBV2_EHIP, "cannot select device %d", ix->device);
   hipStream_t st = (hipStream_t)stream;
+  if (faithful) {   // cbv2_search_grouped_f32's routine; the status stays in the workspace
+    const int32_t cap = std::max<int32_t>(CBV2_RETRIEVE_BAND_CAP, k);
+    const bool band = group_band_taken(ix, g, B, k, r, cap);
+    group_search_f32_layout(ix, g, B, lq, k, r, band ? cap : 0, (uint8_t*)ws, &w, &bw);
+    return search_grouped_f32_impl(ix, g, (const float*)Q, B, lq, k, r, cap, band, w, bw, out_scores, out_groups,
+                                   out_ids, out_chunk_scores, band ? bw.status : nullptr, st);
+  }
+  group_search_layout(ix, g, B, lq, k, scorer, (uint8_t*)ws, &w);
   if (g->groups > 0 && ix->n > 0) {   // (no member anywhere: padding only, no scan)
-    int rc;
-    if (faithful) {   // cbv2_score_f32's full faithful scan: no band
-      F32Ws f;
-      f32_ws_layout(ix, CBV2_F32_SCORE, B, lq, 0, w.f32, &f);
-      if ((rc = split_queries(ix, (const float*)Q, B, lq, &f, st))) return rc;
-      rc = launch_rescore(ix, &f, B, lq, nullptr, nullptr, ix->n, 0, w.S, ix->n, st);
-    } else {
-      rc = score_impl(ix, scorer, Q, B, lq, w.S, ix->n, st, w.ctr);
-    }
-    if (rc) return rc;
+    if (int rc = score_impl(ix, scorer, Q, B, lq, w.S, ix->n, st, w.ctr)) return rc;
   }
   return group_select_impl(g, w.S, ix->n, B, k, r, w.sel, out_scores, out_groups, out_ids, out_chunk_scores, st);
 }
@@ -9048,6 +9558,10 @@ int cbv2_index_set_option(cbv2_index* ix, int32_t option, int64_t value) {
     case CBV2_OPT_FILTER_BAND:
       if (value < 0 || value > 2) return fail(CBV2_EINVAL, "filter band must be 0 (automatic), 1 (on) or 2 (never)");
       ix->filter_band = (int)value;
+      return CBV2_OK;
+    case CBV2_OPT_GROUP_BAND:
+      if (value < 0 || value > 2) return fail(CBV2_EINVAL, "group band must be 0 (automatic), 1 (on) or 2 (never)");
+      ix->group_band = (int)value;
       return CBV2_OK;
     case CBV2_OPT_FILTER_BATCH_CHUNK_DOCS:
       if (value < 0 || value > 0x7fffffffLL) return fail(CBV2_EINVAL, "filter batch chunk docs must be in [0, 2^31)");

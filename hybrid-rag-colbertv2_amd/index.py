@@ -327,8 +327,9 @@ class DocGroups:
     object owns.  ``group_of`` int32 [n]: chunk i's group index in [0, G), or
     -1 for "in no group" (never returned).  ``labels[g]`` is the caller's name
     of group g (default: g itself); ``count`` the number of groups with at
-    least one member.  Read-only; reusable across searches and streams of that
-    index.  Creating one waits for the device once (the upload)."""
+    least one member, ``members`` the number of chunks in some group.
+    Read-only; reusable across searches and streams of that index.  Creating
+    one waits for the device once (the upload)."""
 
     def __init__(self, index: "ColbertIndex", group_of, G: Optional[int] = None, labels: Optional[Sequence] = None):
         L = _lib.lib()
@@ -357,6 +358,7 @@ class DocGroups:
                                         ctypes.byref(h)))
         self._h = h
         self.count = int(L.cbv2_groups_count(h))
+        self.members = int((self.group_of >= 0).sum())   # chunks in some group
 
     def close(self) -> None:
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -949,17 +951,19 @@ class ColbertIndex:
         return per_group
 
     def search_grouped(self, Q: torch.Tensor, k: int, groups: DocGroups, per_group: int = 1,
-                       scorer: str = "maxsim"):
+                       scorer: str = "maxsim", cap: int = BAND_CAP):
         """The top-k GROUPS (documents), each with its best ``per_group`` chunks
         (cbv2_search_grouped; asynchronous): (scores f32 [B, k], group indices
         int32 [B, k], global chunk ids int32 [B, k, per_group], chunk scores f32
         [B, k, per_group]).  A group's score is its best chunk's; groups rank by
         score, then group index; chunks by score, then id.  Padding past the
         number of non-empty groups / a group's size: -inf / -1.  The scores are
-        the unfiltered scorer's bit for bit (the faithful scores on an
-        fp32-faithful index: its full scan, no band).  MaxSim queries of more
-        than 32 tokens take ``score()`` (the blocks' scores summed) and then
-        ``group_topk_rows``."""
+        the unfiltered scorer's bit for bit.  A faithful MaxSim search of at
+        most 32 query tokens goes through cbv2_search_grouped_f32 with band
+        capacity ``cap`` and returns the faithful scores' bits; ``last_band``
+        then holds each row's band size, -1 for a row that took the full
+        faithful scan.  MaxSim queries of more than 32 tokens take ``score()``
+        (the blocks' scores summed) and then ``group_topk_rows``."""
         r = self._check_groups(groups, per_group)
         k = int(k)
         if self._query_blocks(Q, scorer) is not None:
@@ -969,13 +973,28 @@ class ColbertIndex:
         sid = self._scorer(scorer)
         _keep, qptr, qdt, B, lq = self._prep_query(Q, scorer)
         L = _lib.lib()
-        need = int(L.cbv2_search_grouped_workspace_size(self._h, groups._h, B, lq, k, r, sid))
-        if self._ws is None or self._ws.numel() * 4 < need:
-            self._ws = torch.empty(((need + 3) // 4,), dtype=torch.float32, device=self.device)
         out_s = torch.empty((B, k), dtype=torch.float32, device=self.device)
         out_g = torch.empty((B, k), dtype=torch.int32, device=self.device)
         out_i = torch.empty((B, k, r), dtype=torch.int32, device=self.device)
         out_c = torch.empty((B, k, r), dtype=torch.float32, device=self.device)
+        if self.faithful and scorer == "maxsim" and k >= 1:
+            cap = max(int(cap), k)
+            need = int(L.cbv2_search_grouped_f32_workspace_size(self._h, groups._h, B, lq, k, r, cap))
+            if need == 0:
+                raise ValueError(f"cbv2_search_grouped_f32: arguments out of range (B={B}, lq={lq}, k={k}, "
+                                 f"per_group={r}, cap={cap}; the band takes cap in [k, {BAND_CAP}])")
+            if self._ws is None or self._ws.numel() * 4 < need:
+                self._ws = torch.empty(((need + 3) // 4,), dtype=torch.float32, device=self.device)
+            status = torch.empty((B,), dtype=torch.int32, device=self.device)
+            _lib.check(L.cbv2_search_grouped_f32(self._h, groups._h, _keep.data_ptr(), B, lq, k, r, cap,
+                                                 self._ws.data_ptr(), self._ws.numel() * 4, out_s.data_ptr(),
+                                                 out_g.data_ptr(), out_i.data_ptr(), out_c.data_ptr(),
+                                                 status.data_ptr(), _stream_ptr(self.device)))
+            self.last_band = status
+            return out_s, out_g, out_i, out_c
+        need = int(L.cbv2_search_grouped_workspace_size(self._h, groups._h, B, lq, k, r, sid))
+        if self._ws is None or self._ws.numel() * 4 < need:
+            self._ws = torch.empty(((need + 3) // 4,), dtype=torch.float32, device=self.device)
         _lib.check(L.cbv2_search_grouped(self._h, groups._h, sid, qptr, qdt, B, lq, k, r, self._ws.data_ptr(),
                                          self._ws.numel() * 4, out_s.data_ptr(), out_g.data_ptr(), out_i.data_ptr(),
                                          out_c.data_ptr(), _stream_ptr(self.device)))

@@ -246,6 +246,13 @@ int cbv2_index_scan_clock(cbv2_index* index, int64_t* out4, int32_t reset);
  *                        band over the compact row wherever it is supported
  *                        (m > k, k <= 16384), 2 never (one faithful score per
  *                        (query, allowed doc)).  Identical results.
+ *  CBV2_OPT_GROUP_BAND    the grouped faithful search (cbv2_search_grouped_f32,
+ *                        cbv2_search_grouped with f32 queries on a faithful
+ *                        index): 0 automatic (a rule of B, n, k, r and the
+ *                        groups per k), 1 the certified band wherever
+ *                        it is supported (G' > k, k <= 16384, k r <= cap,
+ *                        CBV2_OPT_RESCORE_SPLIT on), 2 never (the full faithful
+ *                        scan of every chunk).  Identical results.
  *  CBV2_OPT_FILTER_BATCH_CHUNK_DOCS  docs per work item of the per-query
  *                        filters' ragged scan (0: automatic, from the batch's
  *                        pair count and the CU count; > 0: for tests).  Read
@@ -271,6 +278,7 @@ int cbv2_index_scan_clock(cbv2_index* index, int64_t* out4, int32_t reset);
 #define CBV2_OPT_FILTER_PATH 14
 #define CBV2_OPT_FILTER_BATCH_CHUNK_DOCS 15
 #define CBV2_OPT_FILTER_BAND 16
+#define CBV2_OPT_GROUP_BAND 17
 int cbv2_index_set_option(cbv2_index* index, int32_t option, int64_t value);
 int cbv2_index_last_scan_plan(const cbv2_index* index, int64_t* out4);
 /* Per-query workgroup lists a cbv2_search of (B, k, scorer) keeps with the
@@ -543,9 +551,46 @@ int cbv2_search_filtered_batch(cbv2_index* index, const cbv2_filter_batch* fb, i
  *    block of the workspace, then the same selection.  Query types, scorers
  *    and index kinds: those of cbv2_search (bf16, MXFP8, REF_MEANPOOL_COSINE,
  *    ld = 128 / 256 / 512 / 1024); on an fp32-faithful index with q_dtype
- *    CBV2_DTYPE_F32 (Q f32 [B][lq][128]) the scores are cbv2_score_f32's: the
- *    full faithful scan, no band.  lq <= 32 for every scorer.  Workspace:
- *    cbv2_search_grouped_workspace_size(index, groups, B, lq, k, r, scorer).
+ *    CBV2_DTYPE_F32 (Q f32 [B][lq][128]) the scores are cbv2_score_f32's, bit
+ *    for bit, reached through cbv2_search_grouped_f32's routine (below) with
+ *    cap = max(CBV2_RETRIEVE_BAND_CAP, k), the status kept in the workspace.
+ *    lq <= 32 for every scorer.  Workspace:
+ *    cbv2_search_grouped_workspace_size(index, groups, B, lq, k, r, scorer),
+ *    computed with the options the search will run under.
+ *  - cbv2_search_grouped_f32: the grouped search of an fp32-faithful index, Q
+ *    f32 [B][lq][128], 1 <= lq <= 32, with a band capacity and a status.
+ *    Results are cbv2_search_grouped's for the same arguments, bit for bit,
+ *    under every value of CBV2_OPT_GROUP_BAND.  out_status int32 [B]: the
+ *    row's global band size, or -1 when the row took the full faithful scan;
+ *    G' == 0 or n == 0 writes padding only and status 0.  Two ways:
+ *    full -- cbv2_score_f32's scan of every chunk into [B][n], then the
+ *      selection: status -1 everywhere, cap not read;
+ *    band -- with T the bf16 scan of hi, S the faithful score and beta(q) >=
+ *      |T - S| for every chunk: the k best groups by T and their leaders (k
+ *      chunks of k distinct groups), lb = the minimum faithful score of those
+ *      chunks (so the k-th group score is >= lb), the band of every member
+ *      chunk with T >= lb - beta (no chunk outside can lead a top-k group),
+ *      its faithful scores, their maximum per group and the row top-k of the
+ *      groups; then per selected group g its top-r chunks by T, s_g = the
+ *      minimum of their faithful scores, the chunks of g with T >= s_g - beta
+ *      (no other chunk of g can be among its best r), their faithful scores
+ *      and the best r.  Needs G' > k, k <= 16384, k r <= cap and
+ *      CBV2_OPT_RESCORE_SPLIT on; other calls take `full`.  With the band, cap
+ *      outside [k, 16384] is CBV2_EINVAL; both lists of a row (the global
+ *      band, the per-group bands together) hold at most cap chunks, and a row
+ *      that exceeds either gets status -1 and is recomputed by `full` on the
+ *      device, every launch gated on the status: no host round trip, the other
+ *      rows untouched.
+ *    An index without a residual is CBV2_ESTATE, a handle of another index, a
+ *    null out_status or a short / misaligned workspace CBV2_EINVAL, all before
+ *    any launch.  Workspace: cbv2_search_grouped_f32_workspace_size(index,
+ *    groups, B, lq, k, r, cap) bytes under the options in force (0 for null
+ *    handles, an index without a residual, B, lq, k, r out of range, or a cap
+ *    outside [k, 16384] where the band would be taken): the search's blocks,
+ *    then for the band 4 r256(4 B) of per-row words, 3 r256(4 B cap) for the
+ *    lists and their scores, 4 r256(4 B k) and 3 r256(4 B k r) for the leaders.
+ *    The sharded calls, cbv2_retrieve_*, cbv2_group_topk_rows and the bf16,
+ *    MXFP8 and mean-pool grouped searches are as they were.
  *  Both compute calls are asynchronous with no host round trip, and both may
  *  be issued on a stream that is capturing a hipGraph when the groups handle
  *  was created before the capture: every replay recomputes them from the
@@ -559,7 +604,8 @@ int cbv2_search_filtered_batch(cbv2_index* index, const cbv2_filter_batch* fb, i
  *  keys / group rows + r256(4 B k) for the selected positions + the row
  *  top-k's workspace of (B, G'); the search adds the scan's counter block in
  *  front, r256(4 B n) for the scores and, on an fp32-faithful index, the query
- *  split of cbv2_score_f32.  The *_size functions are authoritative (0 for a
+ *  split of cbv2_score_f32 and, where f32 queries would take the band, the
+ *  band's blocks (cbv2_search_grouped_f32).  The *_size functions are authoritative (0 for a
  *  null handle or a B, lq, k, r out of range).
  *  How: the scores are reduced over fixed tiles of `order` positions (not over
  *  groups: a group of half the corpus beside singletons stays balanced) by a
@@ -592,6 +638,13 @@ cbv2_search_grouped(cbv2_index* index, const cbv2_groups* groups, int32_t scorer
                         int32_t B, int32_t lq, int32_t k, int32_t r, void* workspace, size_t workspace_bytes,
                         float* out_scores, int32_t* out_groups, int32_t* out_ids, float* out_chunk_scores,
                         void* stream);
+size_t cbv2_search_grouped_f32_workspace_size(const cbv2_index* index, const cbv2_groups* groups, int32_t B,
+                                              int32_t lq, int32_t k, int32_t r, int32_t cap);
+int
+cbv2_search_grouped_f32(cbv2_index* index, const cbv2_groups* groups, const float* Q, int32_t B, int32_t lq,
+                            int32_t k, int32_t r, int32_t cap, void* workspace, size_t workspace_bytes,
+                            float* out_scores, int32_t* out_groups, int32_t* out_ids, float* out_chunk_scores,
+                            int32_t* out_status, void* stream);
 
 /* cbv2_rerank — JinaColBERTRetriever.rerank (local_rag_complete.py:779-800)
  * without re-encoding: the C candidate docs of each query are GATHERED from
