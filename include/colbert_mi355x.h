@@ -62,6 +62,11 @@
  *    candidate C), and inputs are never written.  Pinned by
  *    tests/test_gpu_bounds.py, which runs every device entry point inside
  *    guard bands.
+ *  - Sizes.  Index arrays (tokens, residual) and score matrices larger than
+ *    4 GiB are supported by every entry point, caller-given row strides
+ *    (ld_out, ld) past 2^31 elements included; pinned by
+ *    tests/test_gpu_high_offsets.py, which runs every index path on docs
+ *    astride byte offsets 2^31 and 2^32 of the token arrays.
  *  - Ranking ties are broken deterministically: score descending, then the
  *    lower index in the scored list (doc id for search, candidate position for
  *    rerank).  The reference's torch.topk / argsort (local_rag_complete.py:767,

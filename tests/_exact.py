@@ -266,3 +266,36 @@ class ExactCorpus:
 
     def queries_f32(self):
         return ((self.qhi + self.qlo) / float(ONE)).astype(np.float32)
+
+
+def difference_message(c, kind, ld, what, B, lq, got, want, docs=None, corpus_at=None, place=None):
+    """The failure message of a bit comparison: names the first differing
+    (query, doc), its length, its planted slots and both bit patterns.  ``got``
+    / ``want`` float32 [B, cols]; ``docs`` int [B, cols]: the doc of each
+    column (default: the column); ``corpus_at``: doc -> doc of corpus ``c`` or
+    -1 (default: the docs are c's own); ``place(doc)``: words on where the doc
+    lies."""
+    g = np.ascontiguousarray(got, np.float32).view(np.uint32)
+    w = np.ascontiguousarray(want, np.float32).view(np.uint32)
+    bad = np.argwhere(g != w)
+    b, col = (int(x) for x in bad[0])
+    col_docs = bad[:, 1] if docs is None else np.asarray(docs)[bad[:, 0], bad[:, 1]]
+    d = int(col_docs[0])
+    if corpus_at is None:
+        inside = col_docs[(col_docs >= 0) & (col_docs < c.N)]
+        cd = d if 0 <= d < c.N else -1
+    else:
+        inside = col_docs[(col_docs >= 0) & (col_docs < len(corpus_at))]
+        inside = corpus_at[inside][corpus_at[inside] >= 0]
+        cd = int(corpus_at[d]) if 0 <= d < len(corpus_at) else -1
+    where = f"doc {d}"
+    if cd >= 0:
+        where += (f" (doclens {int(c.doclens[cd])}, planted slots {c.slots[cd].tolist()} = tokens "
+                  f"{c.qj[cd].tolist()} of query {int(c.qb[cd])})")
+    if place is not None:
+        where += f" [{place(d)}]"
+    return (f"{what}: {kind} ld={ld} B={B} lq={lq}: {len(bad)} of {g.size} scores differ from the exact "
+            f"reference; first at query {b}, {where}: got 0x{int(g[b, col]):08x} "
+            f"({float(got[b, col])!r}), want 0x{int(w[b, col]):08x} ({float(want[b, col])!r}); "
+            f"queries {sorted(set(bad[:, 0].tolist()))[:12]}, doclens % 16 of the differing docs "
+            f"{sorted(set((c.doclens[inside] % 16).tolist()))}, doclens {sorted(set(c.doclens[inside].tolist()))[:12]}")

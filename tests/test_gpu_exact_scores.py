@@ -120,24 +120,8 @@ class _Case:
         if got.shape == want.shape and torch.equal(got, want):
             return
         assert got.shape == want.shape, (what, got.shape, want.shape)
-        g = got.cpu().numpy().view(np.uint32)
-        w = want.cpu().numpy().view(np.uint32)
-        bad = np.argwhere(g != w)
-        b, col = (int(x) for x in bad[0])
-        c = self.c
-        col_docs = bad[:, 1] if docs is None else docs.cpu().numpy()[bad[:, 0], bad[:, 1]]
-        d = int(col_docs[0])
-        inside = col_docs[(col_docs >= 0) & (col_docs < c.N)]
-        where = f"doc {d}"
-        if 0 <= d < c.N:
-            where += (f" (doclens {int(c.doclens[d])}, planted slots {c.slots[d].tolist()} = tokens "
-                      f"{c.qj[d].tolist()} of query {int(c.qb[d])})")
-        pytest.fail(
-            f"{what}: {self.kind} ld={self.ld} B={B} lq={lq}: {len(bad)} of {g.size} scores differ from the exact "
-            f"reference; first at query {b}, {where}: got 0x{int(g[b, col]):08x} "
-            f"({got[b, col].item()!r}), want 0x{int(w[b, col]):08x} ({want[b, col].item()!r}); "
-            f"queries {sorted(set(bad[:, 0].tolist()))[:12]}, doclens % 16 of the differing docs "
-            f"{sorted(set((c.doclens[inside] % 16).tolist()))}, doclens {sorted(set(c.doclens[inside].tolist()))[:12]}")
+        pytest.fail(ex.difference_message(self.c, self.kind, self.ld, what, B, lq, got.cpu().numpy(),
+                                          want.cpu().numpy(), None if docs is None else docs.cpu().numpy()))
 
     def options(self, dense=0, split=1):
         self.ix.set_option(_lib.OPT_DENSE_DOCS, dense)
