@@ -942,6 +942,11 @@ int finish_impl(cbv2_index* ix, cbv2_comm* c, const void* Q, int32_t q_dtype, in
                            ? cw + (size_t)B * C : nullptr;   // (below the wait gate and the ready flags)
   uint64_t* const fwd = fw ? (uint64_t*)pd.mb.d + (size_t)B * (2 * (size_t)k + C) : nullptr;
   bool fin_used = false;
+  // a pre-armed launch whose rerank path takes no tagged candidates (one pair
+  // per wave: CBV2_OPT_RESCORE_SPLIT = 0) ran on whatever L.cand held, and its
+  // select_small_kernel has stored final words under this call's tag: the
+  // rerun below then keeps out of them and the host results are copied down
+  bool fin_spent = false;
   rc = CBV2_OK;
   if (!mirrored && hipMemcpyAsync(H.ids, L.ids, (size_t)B * k * 4, hipMemcpyDeviceToHost, st) != hipSuccess)
     rc = err(CBV2_EHIP, "stage-2 ids copy failed");
@@ -960,6 +965,7 @@ int finish_impl(cbv2_index* ix, cbv2_comm* c, const void* Q, int32_t q_dtype, in
     rc = rerank_call(ix, c, kd, Q, B, lq, k, kb, L, L.cand, C, final_k, out_scores, out_ids, out_pos, st);
     armed = cbv2_cand_tagged_used() != 0;   // else it read L.cand (any ids are range-checked): rerun below
     fin_used = armed && fwd && cbv2_final_mirror_used() != 0;
+    fin_spent = !armed && fwd && cbv2_final_mirror_used() != 0;
     cbv2_set_cand_tagged(nullptr, 0, nullptr);
     cbv2_set_final_mirror(nullptr, 0, 0);
   }
@@ -1000,9 +1006,9 @@ int finish_impl(cbv2_index* ix, cbv2_comm* c, const void* Q, int32_t q_dtype, in
       rc = err(CBV2_EHIP, "candidate upload failed");
     }
     if (!rc) {
-      if (fwd) cbv2_set_final_mirror(fwd, pd.seq, final_k);
+      if (fwd && !fin_spent) cbv2_set_final_mirror(fwd, pd.seq, final_k);
       rc = rerank_call(ix, c, kd, Q, B, lq, k, kb, L, cand_d, C, final_k, out_scores, out_ids, out_pos, st);
-      fin_used = fwd && cbv2_final_mirror_used() != 0;
+      fin_used = fwd && !fin_spent && cbv2_final_mirror_used() != 0;
       cbv2_set_final_mirror(nullptr, 0, 0);
     }
   }

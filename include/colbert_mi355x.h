@@ -71,6 +71,9 @@
  *    lower index in the scored list (doc id for search, candidate position for
  *    rerank).  The reference's torch.topk / argsort (local_rag_complete.py:767,
  *    :789) leave tie order unspecified; this is the defined refinement.
+ *    "Score descending" is the order of the scores' order-preserving bit keys
+ *    in every selection (search, rerank, select, merge, groups): -0.0 ranks
+ *    below +0.0, the two are no tie; NaN scores are undefined.
  *
  * Index layout in HBM (see DESIGN.md "Data layout"):
  *    tokens   bf16 [n][ld][d = 128], row-major, 16-byte aligned; ld = 128

@@ -268,6 +268,18 @@ class ExactCorpus:
         return ((self.qhi + self.qlo) / float(ONE)).astype(np.float32)
 
 
+_corpora = {}
+
+
+def cached_corpus(kind, ld, N, B, seed=0):
+    """ExactCorpus(kind, ld, N, B, seed), built once per process (a pool takes
+    4-5 s) and shared by the test files of a session: read-only."""
+    key = (kind, ld, N, B, seed)
+    if key not in _corpora:
+        _corpora[key] = ExactCorpus(kind, ld, N, B, seed=seed)
+    return _corpora[key]
+
+
 def difference_message(c, kind, ld, what, B, lq, got, want, docs=None, corpus_at=None, place=None):
     """The failure message of a bit comparison: names the first differing
     (query, doc), its length, its planted slots and both bit patterns.  ``got``

@@ -51,28 +51,15 @@ import pytest
 import torch
 
 import _exact as ex
+import _exact_shapes as shapes
 from hybrid_rag_colbertv2_amd import _lib
 from hybrid_rag_colbertv2_amd.index import ColbertIndex, _stream_ptr
 from oracle import oracle as orc
 
 pytestmark = pytest.mark.gpu
 
-LDS = (128, 256, 512, 1024)
-SIZE = {128: (600, 65), 256: (300, 65), 512: (200, 40), 1024: (200, 40)}      # ld -> (docs, queries)
+LDS, SIZE, _score_batches = shapes.LDS, shapes.SIZE, shapes.score_batches
 CASES = [(kind, ld) for kind in ex.KINDS for ld in LDS]
-
-
-def _score_batches(kind, ld):
-    bmax = SIZE[ld][1]
-    if kind == "fp32":
-        bs = [1, 2, 3, 4, 5, 6, 7, 8, 9, 13, 14, 16, 17, 20, 21, 31, 32, 33, 64, 65]
-    elif ld == 128 and kind == "bf16":
-        bs = [1, 2, 3, 4, 5, 8, 9, 16, 17, 31, 32, 33, 40, 48, 49, 64, 65]
-    elif ld == 128:
-        bs = [1, 2, 3, 4, 5, 8, 9, 16, 17, 24, 25, 31, 32, 33, 40, 41, 48, 49, 64, 65]
-    else:
-        bs = [1, 2, 3, 4, 5, 8, 9, 31, 32, 33, 64, 65]
-    return [b for b in bs if b <= bmax]
 
 
 def _sweep_batches(kind, ld):
@@ -90,7 +77,7 @@ class _Case:
     def __init__(self, kind, ld, dev):
         n, b = SIZE[ld]
         self.kind, self.ld, self.dev = kind, ld, dev
-        self.c = c = ex.ExactCorpus(kind, ld, n, b, seed=1)
+        self.c = c = ex.cached_corpus(kind, ld, n, b, seed=1)     # shared with tests/test_gpu_walk.py
         self.ref = torch.from_numpy(c.ref.astype(np.float32)).to(dev)           # [B, 32, N]
         self.Q = torch.from_numpy(c.queries_f32()).to(dev)
         self.ix = self.build(c.docs_f32(), c.doclens)
