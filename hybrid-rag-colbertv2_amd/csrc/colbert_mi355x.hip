@@ -5887,7 +5887,10 @@ struct cbv2_index {
   std::mutex mu;  // ring_ev_used, scan_ev / scan_ev_used
   // fp32-faithful index: bf16 residual lo = bf16(x - hi) of the fp32 corpus
   // whose rounding hi is `tokens`, and the split's bounds (max ||x - hi||,
-  // max ||hi||); nullptr = plain bf16 index.
+  // max ||hi||).  has_resid / has_means record that a residual was attached /
+  // the means were built, not the pointers: an empty shard (n == 0) attaches
+  // a null residual and builds null means and is fp32-faithful all the same.
+  bool has_resid = false, has_means = false;
   const uint8_t* resid = nullptr;
   float resid_max = 0.0f, norm_max = 0.0f;
   // Scan timing (cbv2_index_time_scans): while enabled, every MaxSim scan
@@ -6900,7 +6903,7 @@ int check_query(cbv2_index* ix, int32_t scorer, const void* Q, int32_t q_dtype, 
   CBV2_REQUIRE(lq >= 1, "lq must be >= 1 (got %d)", lq);
   CBV2_REQUIRE(aligned16(Q), "query pointer must be 16-byte aligned");
   if (scorer == CBV2_SCORER_MAXSIM) {
-    if (ix->resid != nullptr && q_dtype == CBV2_DTYPE_F32)
+    if (ix->has_resid && q_dtype == CBV2_DTYPE_F32)
       return fail(CBV2_EINVAL, "f32 queries on an fp32-faithful index go through cbv2_score_f32/_search_f32/_rerank_f32");
     if (ix->dtype == CBV2_DTYPE_MXFP8)
       CBV2_REQUIRE(q_dtype == CBV2_DTYPE_MXFP8, "an MXFP8 index takes MXFP8 queries (cbv2_quantize_mxfp8)");
@@ -6909,7 +6912,7 @@ int check_query(cbv2_index* ix, int32_t scorer, const void* Q, int32_t q_dtype, 
     CBV2_REQUIRE(lq <= kLqMax, "maxsim takes at most %d query tokens (got %d)", kLqMax, lq);
   } else if (scorer == CBV2_SCORER_REF_MEANPOOL_COSINE) {
     CBV2_REQUIRE(q_dtype == CBV2_DTYPE_F32, "ref_meanpool_cosine scorer takes f32 queries");
-    if (ix->doc_means == nullptr) return fail(CBV2_ESTATE, "doc means not built (cbv2_index_build_means)");
+    if (!ix->has_means) return fail(CBV2_ESTATE, "doc means not built (cbv2_index_build_means)");
   } else {
     return fail(CBV2_EINVAL, "unknown scorer %d", scorer);
   }
@@ -7117,7 +7120,7 @@ size_t f32_ws_layout(const cbv2_index* ix, int op, int B, int lq, int cap, uint8
 int check_f32(cbv2_index* ix, int op, const float* Q, int32_t B, int32_t lq, int32_t cap, void* ws, size_t wsb,
               F32Ws* w) {
   CBV2_REQUIRE(ix != nullptr, "null index");
-  if (ix->resid == nullptr) return fail(CBV2_ESTATE, "index has no fp32 residual (cbv2_index_attach_residual)");
+  if (!ix->has_resid) return fail(CBV2_ESTATE, "index has no fp32 residual (cbv2_index_attach_residual)");
   CBV2_REQUIRE(Q != nullptr && aligned16(Q), "query pointer must be non-null and 16-byte aligned");
   CBV2_REQUIRE(B >= 1 && B <= 65535, "B must be in [1, 65535] (got %d)", B);
   CBV2_REQUIRE(lq >= 1 && lq <= kLqMax, "lq must be in [1, %d] (got %d)", kLqMax, lq);
@@ -7821,7 +7824,7 @@ FilterPlan filter_plan_m(const cbv2_index* ix, int64_t m_allowed, bool cand, int
   auto r256 = [](size_t b) { return (b + 255) & ~(size_t)255; };
   FilterPlan p;
   p.subset = filter_takes_subset(ix, m_allowed, scorer);
-  const bool f32 = ix->resid != nullptr && scorer == CBV2_SCORER_MAXSIM;
+  const bool f32 = ix->has_resid && scorer == CBV2_SCORER_MAXSIM;
   const int64_t m = m_allowed > 0 ? m_allowed : 1;
   p.off_tk = kCtrBytes;
   p.tk_bytes = r256(topk_ws_bytes(B, m_allowed));
@@ -7842,7 +7845,7 @@ FilterPlan filter_plan_m(const cbv2_index* ix, int64_t m_allowed, bool cand, int
 // size covers both.
 FilterPlan filter_plan(const cbv2_index* ix, const cbv2_filter* f, int32_t B, int32_t lq, int32_t k, int32_t scorer) {
   FilterPlan p = filter_plan_m(ix, f->m, false, B, lq, scorer);
-  if (ix->resid != nullptr && scorer == CBV2_SCORER_MAXSIM && lq <= kLqMax) {
+  if (ix->has_resid && scorer == CBV2_SCORER_MAXSIM && lq <= kLqMax) {
     FilterF32Ws fw;
     p.total = std::max(p.total, filter_f32_layout(ix, f->m, filter_f32_mode(ix, f->m, B, k), B, lq, k,
                                                   std::max<int32_t>(CBV2_RETRIEVE_BAND_CAP, k), nullptr, &fw));
@@ -8321,7 +8324,7 @@ size_t group_search_layout(const cbv2_index* ix, const cbv2_groups* g, int32_t B
   w->S = (float*)(base ? base + off : nullptr);
   off += ((size_t)B * (size_t)(ix->n > 0 ? ix->n : 1) * sizeof(float) + 255) & ~(size_t)255;
   w->f32 = nullptr;
-  if (ix->resid != nullptr && scorer == CBV2_SCORER_MAXSIM && lq <= kLqMax) {
+  if (ix->has_resid && scorer == CBV2_SCORER_MAXSIM && lq <= kLqMax) {
     F32Ws f;
     w->f32 = base ? base + off : nullptr;
     off += f32_ws_layout(ix, CBV2_F32_SCORE, B, lq, 0, nullptr, &f);
@@ -8947,6 +8950,7 @@ int cbv2_index_build_means(cbv2_index* ix, const float* tokens_f32, int32_t ld_s
     if (rc) return rc;
   }
   ix->doc_means = doc_means;
+  ix->has_means = true;
   return CBV2_OK;
 }
 
@@ -9094,7 +9098,7 @@ int cbv2_search_filtered_f32(cbv2_index* ix, const cbv2_filter* f, const float* 
                              int32_t* out_status, void* stream) {
   CBV2_REQUIRE(f != nullptr, "null filter");
   CBV2_REQUIRE(ix != nullptr, "null index");
-  if (ix->resid == nullptr) return fail(CBV2_ESTATE, "index has no fp32 residual (cbv2_index_attach_residual)");
+  if (!ix->has_resid) return fail(CBV2_ESTATE, "index has no fp32 residual (cbv2_index_attach_residual)");
   CBV2_REQUIRE(Q != nullptr && aligned16(Q), "query pointer must be non-null and 16-byte aligned");
   CBV2_REQUIRE(B >= 1 && B <= 65535, "B must be in [1, 65535] (got %d)", B);
   CBV2_REQUIRE(lq >= 1 && lq <= kLqMax, "lq must be in [1, %d] (got %d)", kLqMax, lq);
@@ -9122,7 +9126,7 @@ int cbv2_search_filtered(cbv2_index* ix, const cbv2_filter* f, int32_t scorer, c
                          int32_t* out_ids, void* stream) {
   CBV2_REQUIRE(f != nullptr, "null filter");
   CBV2_REQUIRE(ix != nullptr, "null index");
-  const bool faithful = scorer == CBV2_SCORER_MAXSIM && q_dtype == CBV2_DTYPE_F32 && ix->resid != nullptr;
+  const bool faithful = scorer == CBV2_SCORER_MAXSIM && q_dtype == CBV2_DTYPE_F32 && ix->has_resid;
   if (faithful) {
     CBV2_REQUIRE(Q != nullptr && aligned16(Q), "query pointer must be non-null and 16-byte aligned");
     CBV2_REQUIRE(B >= 1 && B <= 65535, "B must be in [1, 65535] (got %d)", B);
@@ -9262,7 +9266,7 @@ int cbv2_search_filtered_batch(cbv2_index* ix, const cbv2_filter_batch* fb, int3
                                float* out_scores, int32_t* out_ids, void* stream) {
   CBV2_REQUIRE(fb != nullptr, "null filter batch");
   CBV2_REQUIRE(ix != nullptr, "null index");
-  const bool faithful = scorer == CBV2_SCORER_MAXSIM && q_dtype == CBV2_DTYPE_F32 && ix->resid != nullptr;
+  const bool faithful = scorer == CBV2_SCORER_MAXSIM && q_dtype == CBV2_DTYPE_F32 && ix->has_resid;
   if (faithful) {
     CBV2_REQUIRE(Q != nullptr && aligned16(Q), "query pointer must be non-null and 16-byte aligned");
     CBV2_REQUIRE(B >= 1 && B <= 65535, "B must be in [1, 65535] (got %d)", B);
@@ -9420,7 +9424,7 @@ size_t cbv2_search_grouped_workspace_size(const cbv2_index* ix, const cbv2_group
                                           int32_t r, int32_t scorer) {
   if (!ix || !g || B < 1 || lq < 1 || k < 1 || r < 1 || r > kGrpMaxR) return 0;
   GroupSearchWs w;
-  if (ix->resid != nullptr && scorer == CBV2_SCORER_MAXSIM && lq <= kLqMax) {   // f32 queries may take the band
+  if (ix->has_resid && scorer == CBV2_SCORER_MAXSIM && lq <= kLqMax) {   // f32 queries may take the band
     const int32_t cap = std::max<int32_t>(CBV2_RETRIEVE_BAND_CAP, k);
     GroupBandWs bw;
     return group_search_f32_layout(ix, g, B, lq, k, r, group_band_taken(ix, g, B, k, r, cap) ? cap : 0, nullptr, &w,
@@ -9432,7 +9436,7 @@ size_t cbv2_search_grouped_workspace_size(const cbv2_index* ix, const cbv2_group
 size_t cbv2_search_grouped_f32_workspace_size(const cbv2_index* ix, const cbv2_groups* g, int32_t B, int32_t lq,
                                               int32_t k, int32_t r, int32_t cap) {
   if (!ix || !g || B < 1 || B > 65535 || lq < 1 || lq > kLqMax || k < 1 || r < 1 || r > kGrpMaxR) return 0;
-  if (ix->resid == nullptr) return 0;
+  if (!ix->has_resid) return 0;
   const bool wanted = group_band_wanted(ix, g, B, k, r);
   if (wanted && (cap < k || cap > kBandCapMax)) return 0;
   GroupSearchWs w;
@@ -9446,7 +9450,7 @@ int cbv2_search_grouped_f32(cbv2_index* ix, const cbv2_groups* g, const float* Q
                             int32_t* out_ids, float* out_chunk_scores, int32_t* out_status, void* stream) {
   CBV2_REQUIRE(g != nullptr, "null groups handle");
   CBV2_REQUIRE(ix != nullptr, "null index");
-  if (ix->resid == nullptr) return fail(CBV2_ESTATE, "index has no fp32 residual (cbv2_index_attach_residual)");
+  if (!ix->has_resid) return fail(CBV2_ESTATE, "index has no fp32 residual (cbv2_index_attach_residual)");
   CBV2_REQUIRE(Q != nullptr && aligned16(Q), "query pointer must be non-null and 16-byte aligned");
   CBV2_REQUIRE(B >= 1 && B <= 65535, "B must be in [1, 65535] (got %d)", B);
   CBV2_REQUIRE(lq >= 1 && lq <= kLqMax, "lq must be in [1, %d] (got %d)", kLqMax, lq);
@@ -9475,7 +9479,7 @@ int cbv2_search_grouped(cbv2_index* ix, const cbv2_groups* g, int32_t scorer, co
                         int32_t* out_groups, int32_t* out_ids, float* out_chunk_scores, void* stream) {
   CBV2_REQUIRE(g != nullptr, "null groups handle");
   CBV2_REQUIRE(ix != nullptr, "null index");
-  const bool faithful = scorer == CBV2_SCORER_MAXSIM && q_dtype == CBV2_DTYPE_F32 && ix->resid != nullptr;
+  const bool faithful = scorer == CBV2_SCORER_MAXSIM && q_dtype == CBV2_DTYPE_F32 && ix->has_resid;
   if (faithful) {
     CBV2_REQUIRE(Q != nullptr && aligned16(Q), "query pointer must be non-null and 16-byte aligned");
     CBV2_REQUIRE(B >= 1 && B <= 65535, "B must be in [1, 65535] (got %d)", B);
@@ -9590,7 +9594,7 @@ int cbv2_index_last_scan_plan(const cbv2_index* ix, int64_t* out4) {
 int cbv2_index_kind(const cbv2_index* ix, int32_t* dtype, int32_t* faithful) {
   CBV2_REQUIRE(ix != nullptr && dtype != nullptr && faithful != nullptr, "null index or output");
   *dtype = ix->dtype;
-  *faithful = ix->resid != nullptr ? 1 : 0;
+  *faithful = ix->has_resid ? 1 : 0;
   return CBV2_OK;
 }
 
@@ -9738,6 +9742,7 @@ int cbv2_index_attach_residual(cbv2_index* ix, const void* lo, float resid_max, 
   CBV2_REQUIRE(resid_max >= 0.0f && norm_max >= 0.0f && resid_max < 3.0e38f && norm_max < 3.0e38f,
                "bounds must be finite and >= 0");
   ix->resid = (const uint8_t*)lo;
+  ix->has_resid = true;
   ix->resid_max = resid_max;
   ix->norm_max = norm_max;
   return CBV2_OK;
@@ -10078,7 +10083,7 @@ int cbv2_search_f32_finish(cbv2_index* ix, int32_t B, int32_t lq, int32_t k, int
                            const float* lb, float* out_scores, int32_t* out_ids, int32_t* out_status, void* stream) {
   F32Ws w;
   CBV2_REQUIRE(ix != nullptr, "null index");
-  if (ix->resid == nullptr) return fail(CBV2_ESTATE, "index has no fp32 residual (cbv2_index_attach_residual)");
+  if (!ix->has_resid) return fail(CBV2_ESTATE, "index has no fp32 residual (cbv2_index_attach_residual)");
   CBV2_REQUIRE(B >= 1 && B <= 65535 && lq >= 1 && lq <= kLqMax, "bad B / lq");
   CBV2_REQUIRE(k >= 1, "k must be >= 1 (got %d)", k);
   CBV2_REQUIRE(k > kBandCapMax || (cap >= k && cap <= kBandCapMax), "cap must be in [k, %d] (got %d)", kBandCapMax,
@@ -10123,7 +10128,7 @@ int cbv2_rerank_f32_after_search(cbv2_index* ix, const void* search_ws, size_t s
                                  float* out_scores, int32_t* out_ids, int32_t* out_pos, const float* Q, void* stream) {
   CBV2_REQUIRE(cand != nullptr && C >= 1 && k >= 0 && out_scores != nullptr && (k == 0 || out_ids != nullptr),
                "bad candidates / outputs");
-  CBV2_REQUIRE(ix != nullptr && ix->resid != nullptr, "not an fp32-faithful index");
+  CBV2_REQUIRE(ix != nullptr && ix->has_resid, "not an fp32-faithful index");
   CBV2_REQUIRE(B >= 1 && B <= 65535 && lq >= 1 && lq <= kLqMax, "bad B / lq");
   F32Ws sw, w;
   const size_t sneed = f32_ws_layout(ix, CBV2_F32_SEARCH, B, lq, cap, nullptr, &sw);

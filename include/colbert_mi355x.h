@@ -695,7 +695,13 @@ int cbv2_rerank_ws(cbv2_index* index, const void* Q, int32_t B, int32_t lq, cons
  *    device int32 [rows / ld]): rows are docs of ld rows and padding rows
  *    (t >= doclens[doc]) are split but left out of the bounds.
  *  - cbv2_index_attach_residual: a bf16 index built on hi borrows lo and
- *    keeps the two bounds (host floats read back from cbv2_split_f32).
+ *    keeps the two bounds (host floats read back from cbv2_split_f32).  The
+ *    handle remembers THAT a residual was attached, not the pointer: an empty
+ *    shard (n == 0) attaches lo == NULL and is fp32-faithful all the same
+ *    (cbv2_index_kind reports 1, every *_f32 call and the sharded calls take
+ *    their faithful path), so all ranks of a faithful corpus issue the same
+ *    collectives.  Likewise cbv2_index_build_means on n == 0 with null
+ *    pointers leaves the means built (of no docs).
  * Queries are f32 [B][lq][128] (lq <= 32); every call needs a workspace of
  * cbv2_f32_workspace_bytes(index, op, B, lq, cap) bytes (16-B aligned), with
  * cap = the band capacity (SEARCH) or C (RERANK), 0 for SCORE.
