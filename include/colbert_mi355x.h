@@ -18,6 +18,38 @@
  *    call.
  *  - Calls are asynchronous on `stream` (a hipStream_t; NULL = legacy default
  *    stream).  One index handle belongs to one device.
+ *  - Batch sizes.  B is the number of queries (rows) of a call, an int32.
+ *    Bounded, B in [1, 65535] (B = 65536 returns CBV2_EINVAL, launches
+ *    nothing and writes nothing):
+ *      every call that takes f32 queries on an fp32-faithful index:
+ *      cbv2_score_f32, cbv2_search_f32, cbv2_search_f32_begin / _finish,
+ *      cbv2_rerank_f32, cbv2_search_filtered_f32, cbv2_search_grouped_f32,
+ *      and cbv2_search_filtered / cbv2_search_filtered_batch /
+ *      cbv2_search_grouped when q_dtype is CBV2_DTYPE_F32 on such an index;
+ *      cbv2_filter_batch_create, and through its batch -- B must equal the
+ *      batch's -- every cbv2_search_filtered_batch.
+ *      It is the CALL that rejects.  Of the size functions only
+ *      cbv2_filter_batch_bytes and cbv2_search_grouped_f32_workspace_size
+ *      return 0 for B > 65535; the others (cbv2_f32_workspace_bytes,
+ *      cbv2_search_filtered*_workspace_size,
+ *      cbv2_search_grouped_workspace_size) answer for any B >= 1, also
+ *      where the call would reject it.
+ *    Unbounded, B >= 1 (as far as the buffers and the workspace fit memory):
+ *      cbv2_score, cbv2_search, cbv2_rerank, cbv2_rerank_ws, and with bf16 or
+ *      MXFP8 queries cbv2_search_filtered and cbv2_search_grouped;
+ *      cbv2_select_topk, cbv2_topk_rows, cbv2_merge_topk,
+ *      cbv2_group_topk_rows.
+ *    cbv2_retrieve_begin / _finish take the bound of the search they run:
+ *      B >= 1 on a bf16 or MXFP8 index, B in [1, 65535] on an fp32-faithful
+ *      one (cbv2_search_f32 inside begin returns the CBV2_EINVAL).
+ *    Results do not depend on B: above 64 query groups of a scan launch
+ *    (B > 2048 for bf16, 4096 for MXFP8) the dynamic tail gives way to the
+ *    static split unless CBV2_OPT_DYNAMIC_TAIL = 2, and with more query
+ *    groups than resident workgroups one chunk spans the shard; the scores
+ *    are the same bit for bit.  tests/test_gpu_bigbatch.py runs every entry
+ *    point on both sides of each of these points, at 65535 (retrieve up to
+ *    2049), the bounded calls at 65536, and the unbounded selection, score,
+ *    filtered and grouped calls at 65536 and 70001.
  *  - hipGraph capture.  These calls may be issued on a capturing stream, and
  *    every replay of the graph recomputes them from the buffers' contents at
  *    replay time (tests/test_gpu_graph_replay.py replays each of them over

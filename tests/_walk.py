@@ -463,8 +463,10 @@ def _draw_options(rng, theme=None):
     return [int(rng.choice(v)) if rng.random() < 0.15 else int(v[0]) for _, _, v in OPTIONS]
 
 
-def generate(kind, ld, seed, large=False):
-    """The walk (kind, ld, seed): needs no pool, only its sizes."""
+def generate(kind, ld, seed, large=False, n=None):
+    """The walk (kind, ld, seed): needs no pool, only its sizes.  ``n`` (the
+    scripted big-batch walks of tests/_bigbatch.py) replaces the drawn corpus
+    size and leaves every draw before it as it is."""
     w = Walk(kind, ld, seed, large)
     rng = w.rng(0)
     N = w.N
@@ -475,6 +477,8 @@ def generate(kind, ld, seed, large=False):
         w.n = edges[(seed // 2 + 7 * (3 * LDS.index(ld) + ex.KINDS.index(kind))) % len(edges)]
     else:
         w.n = int(rng.integers(1, N + 1))
+    if n is not None:
+        w.n = int(n)
     n = w.n
     w.id_base = int(rng.choice([0, 3, 123456, 2 ** 31 - 2 - n]))
     w.sel = rng.integers(0, N, n)
@@ -520,10 +524,10 @@ def generate(kind, ld, seed, large=False):
     return w
 
 
-def scripted(kind, ld, seed, steps, tag):
+def scripted(kind, ld, seed, steps, tag, large=False, n=None):
     """The corpus and handles of walk (kind, ld, seed) under a written-out list
     of steps (a named regression): the first must be a set_options."""
-    w = generate(kind, ld, seed)
+    w = generate(kind, ld, seed, large, n)
     w.tag, w.steps, opts = tag, [], None
     for st in steps:
         opts = st["values"] if st["ep"] == "set_options" else opts
@@ -553,7 +557,8 @@ def render(i, step):
 
 
 def header(w):
-    fb = ";".join(",".join("N" if x is None else str(x) for x in row) for row in w.batches)
+    fb = ";".join(",".join("N" if x is None else str(x) for x in row[:70]) + (f",... x{len(row)}" if len(row) > 70 else "")
+                  for row in w.batches)
     return (f"walk {w.name}: n={w.n} id_base={w.id_base} sel#{hashlib.sha256(w.sel.tobytes()).hexdigest()[:8]} "
             f"filters={[int(f.mask.sum()) for f in w.filters]} batches=[{fb}] "
             f"groupings={[(g[0], g[2]) for g in w.groupings]} options=({','.join(OPT_NAMES)})")
@@ -569,6 +574,22 @@ def transcripts_hash(walks):
 
 
 # ---------------------------------------------------------------------------- inputs of a step
+def one_period(w, step):
+    """A big-batch step (tests/_bigbatch.py marks it ``tile``) with more queries
+    than the pool has: its queries repeat with the pool's query count P, its
+    drawn inputs are those of the first P rows repeated, its filter batch
+    cycles with a period that divides P -- so row b of every input and of every
+    expected output is row b mod P.  -> the step of the first P rows, or None."""
+    if step.get("tile") and step.get("B", 0) > w.Bp and step["ep"] not in ("set_options", "invalid"):
+        return {key: val for key, val in dict(step, B=w.Bp).items() if key != "tile"}
+    return None
+
+
+def tile_rows(a, B, axis=0):
+    """Rows 0 .. P-1 along ``axis`` repeated to B rows: row b is row b mod P."""
+    return np.take(a, np.arange(B) % a.shape[axis], axis=axis)
+
+
 def query_rows(w, step):
     """The pool queries a step's query buffer holds: q0, q0 + 1, ... (mod the pool's B)."""
     return (step["q0"] + np.arange(step["B"])) % w.Bp
@@ -583,6 +604,9 @@ def ref_rows(w, pool, step):
 def candidates(w, step):
     """int32 [B, C] global ids: docs of the shard with repeats, -1, negative ids
     and ids just outside the shard on either side."""
+    sub = one_period(w, step)
+    if sub is not None:
+        return tile_rows(candidates(w, sub), step["B"])
     rng = w.rng(step["ds"])
     B, C, n, base = step["B"], step["C"], w.n, w.id_base
     cand = (rng.integers(0, n, (B, C)) + base).astype(np.int64)
@@ -624,6 +648,10 @@ def selection_matrix(w, pool, step, cols, k):
 
 def select_inputs(w, pool, step):
     """cbv2_select_topk: (scores [B, C], ids [B, C] or None)."""
+    sub = one_period(w, step)
+    if sub is not None:
+        M, ids = select_inputs(w, pool, sub)
+        return tile_rows(M, step["B"]), None if ids is None else tile_rows(ids, step["B"])
     cols = w.rng(step["ds"]).integers(0, w.n, step["C"])
     M = selection_matrix(w, pool, step, cols, step["k"])
     ids = np.broadcast_to((cols + w.id_base).astype(np.int32), M.shape).copy() if step["ids"] else None
@@ -633,6 +661,9 @@ def select_inputs(w, pool, step):
 def topk_inputs(w, pool, step):
     """cbv2_topk_rows / cbv2_group_topk_rows: scores [B, n + pad], the padding
     columns larger than any score (a read past n would win)."""
+    sub = one_period(w, step)
+    if sub is not None:
+        return tile_rows(topk_inputs(w, pool, sub), step["B"])
     M = selection_matrix(w, pool, step, np.arange(w.n), step["k"])
     pad = step.get("pad", 0)
     return np.concatenate([M, np.full((M.shape[0], pad), 1e30, np.float32)], axis=1) if pad else M
@@ -641,6 +672,10 @@ def topk_inputs(w, pool, step):
 def merge_inputs(w, pool, step):
     """cbv2_merge_topk: G shards of contiguous doc ranges, each one's sorted
     top-k list (-inf / -1 padded): scores [G, B, k], global ids [G, B, k]."""
+    sub = one_period(w, step)
+    if sub is not None:
+        M, in_s, in_i = merge_inputs(w, pool, sub)
+        return tile_rows(M, step["B"]), tile_rows(in_s, step["B"], 1), tile_rows(in_i, step["B"], 1)
     M = selection_matrix(w, pool, step, np.arange(w.n), step["k"])
     G, k = step["G"], step["k"]
     cuts = np.linspace(0, w.n, G + 1).astype(np.int64)
@@ -655,6 +690,9 @@ def merge_inputs(w, pool, step):
 def lexical_ids(w, step):
     """The stage-1 lists of a retrieve: int32 [B, kb] global ids, rows with a -1
     tail, ids outside the shard and repeats."""
+    sub = one_period(w, step)
+    if sub is not None:
+        return tile_rows(lexical_ids(w, sub), step["B"])
     rng = w.rng(step["ds"] + 2)
     B, kb = step["B"], step["kb"]
     lex = (rng.integers(0, w.n, (B, kb)) + w.id_base).astype(np.int64)
@@ -708,10 +746,24 @@ def grouped_expect(S, w, step):
     return {"scores": s, "groups": g, "ids": i, "chunk_scores": c}
 
 
-def expected(w, pool, step):
+def expected(w, pool, step, tiled=True):
     """name -> the array the call must write, bit for bit; "rc" the return code;
-    ("status", lo [B], cap) for a faithful call's status word."""
+    ("status", lo [B], cap) for a faithful call's status word.  A big-batch
+    step (one_period) is answered for one period of its rows and repeated;
+    ``tiled`` = False answers it row by row from the same inputs
+    (tests/test_bigbatch_model.py pins the two against each other)."""
     ep = step["ep"]
+    sub = one_period(w, step) if tiled else None
+    if sub is not None:
+        B, out = step["B"], {}
+        for name, x in expected(w, pool, sub).items():
+            if name in ("rc", "between"):                      # the call between has its own B (and its own period)
+                out[name] = x
+            elif isinstance(x, tuple):
+                out[name] = (x[0], tile_rows(x[1], B), x[2])
+            else:
+                out[name] = tile_rows(x, B)
+        return out
     if ep == "set_options":
         return {"rc": 0}
     if ep == "invalid":
@@ -739,7 +791,7 @@ def expected(w, pool, step):
         if ep != "search":
             out["status"] = status_range(S, k, step["cap"])
         if "between" in step:
-            out["between"] = expected(w, pool, step["between"])
+            out["between"] = expected(w, pool, step["between"], tiled)
     elif ep in ("rerank", "rerank_ws", "rerank_f32"):
         out.update(rerank_expect(S, candidates(w, step), k, w))
     elif ep in ("search_filtered", "search_filtered_f32"):
@@ -751,7 +803,8 @@ def expected(w, pool, step):
             else:
                 out["status"] = np.zeros(S.shape[0], np.int32)
     elif ep == "search_filtered_batch":
-        rows = [np.arange(w.n) if f is None else np.flatnonzero(w.filters[f].mask) for f in w.batches[step["fb"]]]
+        rows = [np.arange(w.n) if f is None else np.flatnonzero(w.filters[f].mask)
+                for f in w.batches[step["fb"]][: S.shape[0]]]
         out["scores"], out["ids"] = filtered_expect(S, rows, k, w)
     elif ep in ("search_grouped", "search_grouped_f32"):
         out.update(grouped_expect(S, w, step))

@@ -117,10 +117,13 @@ def pool_dev(kind, ld, dev):
 
 
 class Buffers:
-    def __init__(self, dev, ws_bytes):
+    """q_bytes / host_bytes: the query buffer and the pinned host buffer of
+    walks with larger batches than 65 (tests/test_gpu_bigbatch.py)."""
+
+    def __init__(self, dev, ws_bytes, q_bytes=Q_BYTES, host_bytes=HOST_BYTES):
         self.ws = [torch.empty((ws_bytes,), dtype=torch.uint8, device=dev) for _ in range(2)]
-        self.q = torch.zeros((Q_BYTES,), dtype=torch.uint8, device=dev)
-        self.host = torch.empty((HOST_BYTES,), dtype=torch.uint8, pin_memory=True)
+        self.q = torch.zeros((q_bytes,), dtype=torch.uint8, device=dev)
+        self.host = torch.empty((host_bytes,), dtype=torch.uint8, pin_memory=True)
         assert all(t.data_ptr() % 256 == 0 for t in self.ws + [self.q])
         self.poison()
 
@@ -188,7 +191,8 @@ class Gpu:
     def diagnose(self, i, step, want):
         """The failing step alone on a fresh index and a fresh zeroed workspace."""
         torch.cuda.synchronize()
-        fresh = Gpu(self.dev, Buffers(self.dev, self.bufs.ws[0].numel()), zeroed=True)
+        fresh = Gpu(self.dev, Buffers(self.dev, self.bufs.ws[0].numel(), self.bufs.q.numel(), self.bufs.host.numel()),
+                    zeroed=True)
         try:
             fresh.start(self.w, self.pool, opts=step["opts"])
             msg = wk.compare(fresh, fresh.call(i, step), want)
@@ -221,7 +225,7 @@ class Gpu:
         """The step's queries written in place into the walk's one query buffer -> its pointer."""
         B, lq = step["B"], min(max(step["lq"], 1), wk.LQ_MAX)
         rows = torch.from_numpy((step["q0"] + np.arange(B)) % self.w.Bp).to(self.dev)
-        Q = self.pd.Q.index_select(0, rows)[:, :lq].contiguous()
+        Q = self.pd.Q[:, :lq].index_select(0, rows).contiguous()
         qb = self.bufs.q
         if self.w.kind == "fp32":
             qb[: Q.numel() * 4].view(torch.float32).copy_(Q.reshape(-1))

@@ -229,7 +229,7 @@ class Brute:
             if ep == "search_filtered_f32":
                 out["status"] = np.full(len(rows), -1 if len(al) else 0, np.int32)
         elif ep == "search_filtered_batch":
-            lists = [ids if f is None else self.allowed(w.filters[f]) for f in w.batches[step["fb"]]]
+            lists = [ids if f is None else self.allowed(w.filters[f]) for f in w.batches[step["fb"]][: len(rows)]]
             out["scores"], out["ids"] = self.filtered(rows, lists, k)
         elif ep in ("search_grouped", "search_grouped_f32"):
             out.update(self.grouped(rows, step))
