@@ -84,6 +84,15 @@ _SIGS = {
     "cbv2_search_grouped_f32_workspace_size": (_sz, [_p, _p, _i32, _i32, _i32, _i32, _i32]),
     "cbv2_search_grouped_f32": (ctypes.c_int, [_p, _p, _p, _i32, _i32, _i32, _i32, _i32, _p, _sz, _p, _p, _p, _p, _p,
                                                _p]),
+    "cbv2_group_chunks_workspace_size": (_sz, [_i32, _i32]),
+    "cbv2_group_chunks_rows": (ctypes.c_int, [_p, _p, _i64, _i32, _i32, _i32, _p, _p, _sz, _p, _p, _p]),
+    "cbv2_merge_group_topk": (ctypes.c_int, [_p, _p, _i32, _i32, _i32, _i64, _p, _p, _p]),
+    "cbv2_merge_group_chunks": (ctypes.c_int, [_p, _p, _i32, _i32, _i32, _i32, _i64, _p, _p, _p]),
+    "cbv2_group_sharded_workspace_bytes": (_sz, [_p, _p, _i32, _i32, _i32]),
+    "cbv2_group_topk_sharded": (ctypes.c_int, [_p, _p, _p, _i64, _i32, _i32, _i32, _p, _sz, _p, _p, _p, _p, _p]),
+    "cbv2_search_grouped_sharded_workspace_size": (_sz, [_p, _p, _p, _i32, _i32, _i32, _i32, _i32]),
+    "cbv2_search_grouped_sharded": (ctypes.c_int, [_p, _p, _p, _i32, _p, _i32, _i32, _i32, _i32, _i32, _p, _sz, _p,
+                                                   _p, _p, _p, _p]),
     "cbv2_rerank": (ctypes.c_int, [_p, _p, _i32, _i32, _p, _i32, _i32, _p, _p, _p, _p]),
     "cbv2_rerank_workspace_bytes": (_sz, [_i32, _i32]),
     "cbv2_rerank_ws": (ctypes.c_int, [_p, _p, _i32, _i32, _p, _i32, _i32, _p, _sz, _p, _p, _p, _p]),

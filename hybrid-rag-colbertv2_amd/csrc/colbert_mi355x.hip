@@ -8206,6 +8206,160 @@ __global__ __launch_bounds__(256) void group_fill_empty_kernel(float* __restrict
   }
 }
 
+// ---------------------------------------------------------------------------
+// Sharded grouped search (csrc/sharded.cpp: cbv2_group_topk_sharded,
+// cbv2_search_grouped_sharded): the local chunk stage's mapping
+// and the two merges of the gathered lists.
+// ---------------------------------------------------------------------------
+constexpr int kMgMaxKeys = 16384;   // G * k limit of merge_group_topk_kernel: 128 KiB of keys in dynamic LDS
+constexpr int kMgThreads = 1024;    // its largest workgroup
+constexpr int kMgPer = kMgMaxKeys / kMgThreads;   // keys per thread at the limit
+constexpr int kMcMaxG = 64;         // ranks merge_group_chunks_kernel takes (a wave's lanes)
+
+// sel [total]: the caller's group indices (-1: padding) -> their positions in
+// labels[0 .. groups) (ascending: a binary search), -1 for padding, an index
+// outside [0, G) and a group without a member on this shard.
+__global__ __launch_bounds__(256) void group_map_kernel(const int32_t* __restrict__ sel, int64_t total,
+                                                        const int32_t* __restrict__ labels, int32_t groups, int32_t G,
+                                                        int32_t* __restrict__ pos) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int32_t e = sel[i];
+    int32_t p = -1;
+    if (e >= 0 && e < G) {
+      int32_t lo = 0, hi = groups;   // the first position whose label is >= e
+      while (lo < hi) {
+        const int32_t mid = lo + ((hi - lo) >> 1);
+        if (labels[mid] < e) lo = mid + 1; else hi = mid;
+      }
+      if (lo < groups && labels[lo] == e) p = lo;
+    }
+    pos[i] = p;
+  }
+}
+
+// Descending bitonic sort of a[0 .. n), n a power of two, by the whole
+// workgroup; ends with a barrier.
+__device__ __forceinline__ void mg_sort_desc(uint64_t* a, int n) {
+  for (int size = 2; size <= n; size <<= 1) {
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      __syncthreads();
+      for (int t = threadIdx.x; t < (n >> 1); t += blockDim.x) {
+        const int i = ((t & ~(stride - 1)) << 1) | (t & (stride - 1)), j = i + stride;
+        const bool desc = (i & size) == 0;
+        const uint64_t x = a[i], y = a[j];
+        if (x != y && (x < y) == desc) {
+          a[i] = y;
+          a[j] = x;
+        }
+      }
+    }
+  }
+  __syncthreads();
+}
+
+// One workgroup per row b over the G gathered lists of k (score, group) pairs
+// (group < 0: padding).  Sort by (group ascending, score descending) as the
+// key ~group << 32 | f2u(score), descending; the head of every run of one group
+// is that group's maximum and becomes the rank key f2u(score) << 32 | ~group
+// (the two halves swapped), every other entry 0; a second sort ranks the heads
+// (score descending, group ascending) and the first k are the row's result.
+// np2: the power of two >= G * k (<= kMgMaxKeys); blockDim.x * kMgPer >= np2.
+__global__ __launch_bounds__(kMgThreads) void merge_group_topk_kernel(const float* __restrict__ in_s,
+                                                                      const int32_t* __restrict__ in_g, int G, int B,
+                                                                      int k, int64_t stride, int np2,
+                                                                      float* __restrict__ out_s,
+                                                                      int32_t* __restrict__ out_g) {
+  extern __shared__ uint64_t mg_keys[];
+  const int tid = threadIdx.x, nth = blockDim.x, N = G * k;
+  for (int b = blockIdx.x; b < B; b += gridDim.x) {   // block-uniform
+    for (int t = tid; t < np2; t += nth) {
+      uint64_t key = 0ull;
+      if (t < N) {
+        const size_t src = (size_t)(t / k) * (size_t)stride + (size_t)b * k + (size_t)(t % k);
+        const int32_t gr = in_g[src];
+        if (gr >= 0) key = ((uint64_t)(~(uint32_t)gr) << 32) | f2u(in_s[src]);
+      }
+      mg_keys[t] = key;
+    }
+    mg_sort_desc(mg_keys, np2);
+    uint64_t head[kMgPer];
+#pragma unroll
+    for (int u = 0; u < kMgPer; ++u) {
+      const int t = tid + u * nth;
+      head[u] = 0ull;
+      if (t < np2) {
+        const uint64_t x = mg_keys[t];
+        const bool first = x != 0ull && (t == 0 || (mg_keys[t - 1] >> 32) != (x >> 32));
+        if (first) head[u] = (x << 32) | (x >> 32);
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < kMgPer; ++u) {
+      const int t = tid + u * nth;
+      if (t < np2) mg_keys[t] = head[u];
+    }
+    mg_sort_desc(mg_keys, np2);
+    for (int j = tid; j < k; j += nth) {
+      const uint64_t key = mg_keys[j];   // k <= G * k <= np2
+      out_s[(size_t)b * k + j] = key != 0ull ? u2f((uint32_t)(key >> 32)) : neg_inf();
+      out_g[(size_t)b * k + j] = key != 0ull ? (int32_t)(~(uint32_t)key) : -1;
+    }
+    __syncthreads();   // the keys are read before the next row overwrites them
+  }
+}
+
+// One wave per (row b, selected slot j) over the G gathered lists of r (chunk
+// id, score) pairs of that slot (id < 0: padding): the best r of the G * r by
+// rank_key(score, id) -- score descending, then id ascending; a -inf chunk keeps
+// its id and ranks after every finite one.  Lane g holds rank g's list; r
+// rounds take the largest key of the wave and every lane drops it (a chunk
+// lives on one rank, so a key occurs once; equal pairs would collapse to one).
+__global__ __launch_bounds__(256) void merge_group_chunks_kernel(const int32_t* __restrict__ in_i,
+                                                                 const float* __restrict__ in_c, int G, int64_t slots,
+                                                                 int r, int64_t stride, int32_t* __restrict__ out_i,
+                                                                 float* __restrict__ out_c) {
+  const int lane = threadIdx.x & 63;
+  const int64_t wave0 = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  const int64_t nwaves = (int64_t)gridDim.x * (blockDim.x >> 6);
+  for (int64_t slot = wave0; slot < slots; slot += nwaves) {   // wave-uniform
+    uint64_t l[kGrpMaxR];
+#pragma unroll
+    for (int t = 0; t < kGrpMaxR; ++t) {
+      l[t] = 0ull;
+      if (lane < G && t < r) {
+        const size_t src = (size_t)lane * (size_t)stride + (size_t)slot * r + t;
+        const int32_t id = in_i[src];
+        if (id >= 0) l[t] = rank_key(in_c[src], (uint32_t)id);
+      }
+    }
+    for (int t = 0; t < r; ++t) {
+      uint64_t m = l[0];
+#pragma unroll
+      for (int i = 1; i < kGrpMaxR; ++i) m = l[i] > m ? l[i] : m;
+#pragma unroll
+      for (int d = 32; d >= 1; d >>= 1) {
+        const uint64_t o = __shfl_xor((unsigned long long)m, d);
+        m = o > m ? o : m;
+      }
+#pragma unroll
+      for (int i = 0; i < kGrpMaxR; ++i)
+        if (l[i] == m) l[i] = 0ull;
+      if (lane == 0) {
+        out_i[(size_t)slot * r + t] = m != 0ull ? (int32_t)(~(uint32_t)m) : -1;
+        out_c[(size_t)slot * r + t] = m != 0ull ? u2f((uint32_t)(m >> 32)) : neg_inf();
+      }
+    }
+  }
+}
+
+// out_s[slot] = cs[slot][0]: a merged group's score is its best chunk's.
+__global__ __launch_bounds__(256) void group_lead_scores_kernel(const float* __restrict__ cs, int64_t slots, int r,
+                                                                float* __restrict__ out_s) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < slots; i += (int64_t)gridDim.x * blockDim.x)
+    out_s[i] = cs[(size_t)i * r];
+}
+
 // Workspace of the selection: the keys / group-score rows [B][G'], the row
 // top-k's positions [B][k] and the row top-k's own workspace, each rounded up
 // to 256 B.
@@ -9418,6 +9572,144 @@ int cbv2_group_topk_rows(const cbv2_groups* g, const float* scores, int64_t ld, 
   if (!dg.ok) return fail(CBV2_EHIP, "cannot select device %d", g->device);
   return group_select_impl(g, scores, ld, B, k, r, w, out_scores, out_groups, out_ids, out_chunk_scores,
                            (hipStream_t)stream);
+}
+
+// The local chunk stage of the sharded grouped search: the positions of the
+// selected groups [B][k], then group_finish_kernel's group indices [B][k]
+// (scratch: the caller knows them), each rounded up to 256 B.
+size_t cbv2_group_chunks_workspace_size(int32_t B, int32_t k) {
+  if (B < 1 || k < 1) return 0;
+  return 2 * (((size_t)B * k * sizeof(int32_t) + 255) & ~(size_t)255);
+}
+
+int cbv2_group_chunks_rows(const cbv2_groups* g, const float* scores, int64_t ld, int32_t B, int32_t k, int32_t r,
+                           const int32_t* sel_groups, void* ws, size_t ws_bytes, int32_t* out_ids,
+                           float* out_chunk_scores, void* stream) {
+  CBV2_REQUIRE(g != nullptr, "null groups handle");
+  CBV2_REQUIRE(B >= 1, "B must be >= 1 (got %d)", B);
+  CBV2_REQUIRE(k >= 1, "k must be >= 1 (got %d)", k);
+  CBV2_REQUIRE(r >= 1 && r <= kGrpMaxR, "r must be in [1, %d] (got %d)", kGrpMaxR, r);
+  CBV2_REQUIRE(sel_groups && out_ids && out_chunk_scores, "null selection / outputs");
+  CBV2_REQUIRE(g->members == 0 || scores != nullptr, "null scores");
+  CBV2_REQUIRE(ld >= g->n, "ld (%lld) < n (%lld)", (long long)ld, (long long)g->n);
+  const size_t need = cbv2_group_chunks_workspace_size(B, k);
+  CBV2_REQUIRE(ws != nullptr && ws_bytes >= need && aligned16(ws), "workspace too small or misaligned (%zu < %zu)",
+               ws_bytes, need);
+  DeviceGuard dg(g->device);
+  if (!dg.ok) return fail(CBV2_EHIP, "cannot select device %d", g->device);
+  hipStream_t st = (hipStream_t)stream;
+  int32_t* pos = (int32_t*)ws;
+  int32_t* grp = (int32_t*)((uint8_t*)ws + need / 2);
+  const int64_t slots = (int64_t)B * k;
+  hipLaunchKernelGGL(group_map_kernel, dim3((unsigned)std::min<int64_t>((slots + 255) / 256, 65535)), dim3(256), 0, st,
+                     sel_groups, slots, g->labels, g->groups, g->G, pos);
+  if (int rc = launch_check("group_map_kernel")) return rc;
+  hipLaunchKernelGGL(group_finish_kernel, dim3((unsigned)std::min<int32_t>(k, 1 << 20), (unsigned)std::min(B, 65535)),
+                     dim3(kGfThreads), 0, st, scores, ld, B, k, r, g->order, g->offsets, g->labels, g->groups,
+                     g->id_base, pos, grp, out_ids, out_chunk_scores);
+  return launch_check("group_finish_kernel");
+}
+
+int cbv2_merge_group_topk(const float* in_scores, const int32_t* in_groups, int32_t G, int32_t B, int32_t k,
+                          int64_t stride, float* out_scores, int32_t* out_groups, void* stream) {
+  CBV2_REQUIRE(in_scores && in_groups && out_scores && out_groups, "null pointer");
+  CBV2_REQUIRE(G >= 1 && G <= 64, "G must be in [1, 64] (got %d)", G);
+  CBV2_REQUIRE(B >= 1, "B must be >= 1 (got %d)", B);
+  CBV2_REQUIRE(k >= 1, "k must be >= 1 (got %d)", k);
+  CBV2_REQUIRE(stride >= (int64_t)B * k, "stride (%lld) < B k (%lld)", (long long)stride, (long long)B * k);
+  if ((int64_t)G * k > kMgMaxKeys)
+    return fail(CBV2_EUNSUPPORTED, "the grouped merge takes G k <= %d (got %d x %d)", kMgMaxKeys, G, k);
+  int np2 = 1;
+  while (np2 < G * k) np2 <<= 1;
+  const int threads = std::min(kMgThreads, std::max(64, np2 / 2));
+  const size_t dyn = (size_t)np2 * sizeof(uint64_t);
+  if (dyn > 32768)
+    CBV2_HIP(hipFuncSetAttribute((const void*)merge_group_topk_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                 kMgMaxKeys * (int)sizeof(uint64_t)));
+  hipLaunchKernelGGL(merge_group_topk_kernel, dim3((unsigned)std::min(B, 1 << 20)), dim3((unsigned)threads), dyn,
+                     (hipStream_t)stream, in_scores, in_groups, G, B, k, stride, np2, out_scores, out_groups);
+  return launch_check("merge_group_topk_kernel");
+}
+
+int cbv2_merge_group_chunks(const int32_t* in_ids, const float* in_cs, int32_t G, int32_t B, int32_t k, int32_t r,
+                            int64_t stride, int32_t* out_ids, float* out_cs, void* stream) {
+  CBV2_REQUIRE(in_ids && in_cs && out_ids && out_cs, "null pointer");
+  CBV2_REQUIRE(G >= 1 && G <= kMcMaxG, "G must be in [1, %d] (got %d)", kMcMaxG, G);
+  CBV2_REQUIRE(B >= 1, "B must be >= 1 (got %d)", B);
+  CBV2_REQUIRE(k >= 1, "k must be >= 1 (got %d)", k);
+  CBV2_REQUIRE(r >= 1 && r <= kGrpMaxR, "r must be in [1, %d] (got %d)", kGrpMaxR, r);
+  CBV2_REQUIRE(stride >= (int64_t)B * k * r, "stride (%lld) < B k r (%lld)", (long long)stride,
+               (long long)B * k * r);
+  const int64_t slots = (int64_t)B * k;
+  hipLaunchKernelGGL(merge_group_chunks_kernel, dim3((unsigned)std::min<int64_t>((slots + 3) / 4, 1 << 20)), dim3(256),
+                     0, (hipStream_t)stream, in_ids, in_cs, G, slots, r, stride, out_ids, out_cs);
+  return launch_check("merge_group_chunks_kernel");
+}
+
+// Internal (sharded.cpp): out_scores[b][j] = chunk_scores[b][j][0].
+int cbv2_group_lead_scores(const float* chunk_scores, int32_t B, int32_t k, int32_t r, float* out_scores,
+                           void* stream) {
+  CBV2_REQUIRE(chunk_scores && out_scores && B >= 1 && k >= 1 && r >= 1, "bad arguments");
+  const int64_t slots = (int64_t)B * k;
+  hipLaunchKernelGGL(group_lead_scores_kernel, dim3((unsigned)std::min<int64_t>((slots + 255) / 256, 65535)), dim3(256),
+                     0, (hipStream_t)stream, chunk_scores, slots, r, out_scores);
+  return launch_check("group_lead_scores_kernel");
+}
+
+// Internal (sharded.cpp): the score stage of cbv2_search_grouped_sharded -- the
+// scorer's scores of every local chunk into a [B][n] block (ld = n) of `ws`:
+// [the scan's counter block | scores | cbv2_score_f32's query split on an
+// index with a residual].  Query types, scorers and checks: cbv2_search_grouped's;
+// f32 queries on an fp32-faithful index take the FULL faithful scan
+// (cbv2_score_f32's routine), never the certified band.  *scores_out: the
+// block (valid when n > 0 and some group has a member; nothing is scored
+// otherwise).
+size_t cbv2_grouped_scores_bytes(const cbv2_index* ix, int32_t B, int32_t lq, int32_t scorer) {
+  if (!ix || B < 1 || lq < 1) return 0;
+  size_t off = kCtrBytes + (((size_t)B * (size_t)(ix->n > 0 ? ix->n : 1) * sizeof(float) + 255) & ~(size_t)255);
+  if (ix->has_resid && scorer == CBV2_SCORER_MAXSIM && lq <= kLqMax) {
+    F32Ws f;
+    off += f32_ws_layout(ix, CBV2_F32_SCORE, B, lq, 0, nullptr, &f);
+  }
+  return off;
+}
+
+int cbv2_grouped_scores(cbv2_index* ix, const cbv2_groups* g, int32_t scorer, const void* Q, int32_t q_dtype,
+                        int32_t B, int32_t lq, void* ws, size_t ws_bytes, float** scores_out, int64_t* ld_out,
+                        void* stream) {
+  CBV2_REQUIRE(g != nullptr, "null groups handle");
+  CBV2_REQUIRE(ix != nullptr, "null index");
+  CBV2_REQUIRE(scores_out && ld_out, "null outputs");
+  const bool faithful = scorer == CBV2_SCORER_MAXSIM && q_dtype == CBV2_DTYPE_F32 && ix->has_resid;
+  if (faithful) {
+    CBV2_REQUIRE(Q != nullptr && aligned16(Q), "query pointer must be non-null and 16-byte aligned");
+    CBV2_REQUIRE(B >= 1 && B <= 65535, "B must be in [1, 65535] (got %d)", B);
+    CBV2_REQUIRE(lq >= 1 && lq <= kLqMax, "lq must be in [1, %d] (got %d)", kLqMax, lq);
+  } else if (int rc = check_query(ix, scorer, Q, q_dtype, B, lq)) {
+    return rc;
+  }
+  CBV2_REQUIRE(lq <= kLqMax, "a grouped search takes at most %d query tokens (got %d)", kLqMax, lq);
+  CBV2_REQUIRE(g->n == ix->n && g->id_base == ix->id_base && g->device == ix->device,
+               "the groups were created for another index (n %lld / %lld, id_base %lld / %lld, device %d / %d)",
+               (long long)g->n, (long long)ix->n, (long long)g->id_base, (long long)ix->id_base, g->device, ix->device);
+  const size_t need = cbv2_grouped_scores_bytes(ix, B, lq, scorer);
+  CBV2_REQUIRE(ws != nullptr && ws_bytes >= need && aligned16(ws), "workspace too small or misaligned (%zu < %zu)",
+               ws_bytes, need);
+  float* S = (float*)((uint8_t*)ws + kCtrBytes);
+  *scores_out = S;
+  *ld_out = ix->n > 0 ? ix->n : 1;
+  if (g->groups == 0 || ix->n == 0) return CBV2_OK;   // (no member anywhere: padding only, no scan)
+  DeviceGuard dg(ix->device);
+  if (!dg.ok) return fail(CBV2_EHIP, "cannot select device %d", ix->device);
+  hipStream_t st = (hipStream_t)stream;
+  if (faithful) {
+    F32Ws f;
+    const size_t s_bytes = ((size_t)B * (size_t)ix->n * sizeof(float) + 255) & ~(size_t)255;
+    f32_ws_layout(ix, CBV2_F32_SCORE, B, lq, 0, (uint8_t*)ws + kCtrBytes + s_bytes, &f);
+    if (int rc = split_queries(ix, (const float*)Q, B, lq, &f, st)) return rc;
+    return launch_rescore(ix, &f, B, lq, nullptr, nullptr, ix->n, 0, S, ix->n, st);
+  }
+  return score_impl(ix, scorer, Q, B, lq, S, ix->n, st, (int*)ws);
 }
 
 size_t cbv2_search_grouped_workspace_size(const cbv2_index* ix, const cbv2_groups* g, int32_t B, int32_t lq, int32_t k,

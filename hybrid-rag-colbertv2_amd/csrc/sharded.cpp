@@ -28,6 +28,11 @@
 // the unsharded faithful search and rerank bit for bit (the merge completes
 // the exact global top-k; any lower bound of the k-th score keeps it exact).
 //
+// The grouped search (cbv2_group_topk_sharded, cbv2_search_grouped_sharded;
+// DESIGN.md §3.9) is a protocol of its own, two all-gathers: the local top-k
+// groups, merged by maximum per group, then every rank's best chunks of the
+// groups that merge selected, merged per slot.
+//
 // No reference counterpart: the reference is single-process.
 // RCCL is resolved with dlsym from the library that created the communicator
 // (passed by path; NULL = "librccl.so"), so the borrowed ncclComm_t and the
@@ -57,6 +62,12 @@ extern "C" int cbv2_rerank_f32_after_search(cbv2_index* ix, const void* search_w
                                             int32_t B, int32_t lq, const int32_t* cand, int32_t C, int32_t k, void* ws,
                                             size_t wsb, float* out_scores, int32_t* out_ids, int32_t* out_pos,
                                             const float* Q, void* stream);
+extern "C" int cbv2_group_lead_scores(const float* chunk_scores, int32_t B, int32_t k, int32_t r, float* out_scores,
+                                      void* stream);
+extern "C" size_t cbv2_grouped_scores_bytes(const cbv2_index* ix, int32_t B, int32_t lq, int32_t scorer);
+extern "C" int cbv2_grouped_scores(cbv2_index* ix, const cbv2_groups* g, int32_t scorer, const void* Q, int32_t q_dtype,
+                                   int32_t B, int32_t lq, void* ws, size_t ws_bytes, float** scores_out,
+                                   int64_t* ld_out, void* stream);
 
 namespace {
 // The RCCL entry points used here (rccl.h: ncclResult_t is an int enum,
@@ -512,6 +523,137 @@ int cbv2_rerank_sharded_prescored(cbv2_index* ix, cbv2_comm* c, int32_t B, int32
   const Layout L = layout(ix, c, B, k, kb, workspace);
   return cbv2_prescored_select(L.recv, c->nranks, (int64_t)L.blk, B, k, kb, cand, C, final_k, out_scores, out_ids,
                                out_pos, misses, stream);
+}
+
+// ---------------------------------------------------------------------------
+// Sharded grouped search (include/colbert_mi355x.h): two
+// all-gathers -- the local top-k groups, then the local best chunks of the k
+// groups the first merge selected.
+// Workspace: [local selection (cbv2_group_topk_rows, r = 1) | its chunk ids
+// B*k | its chunk scores B*k (both unused) | send 1: scores B*k, groups B*k |
+// recv 1: G blocks | local chunk stage | send 2: ids B*k*r, scores B*k*r |
+// recv 2: G blocks], every part rounded up to 256 B.
+namespace {
+constexpr int64_t kGroupMergeMax = 16384;   // G * k of cbv2_merge_group_topk
+
+struct GroupLayout {
+  size_t sel_bytes, chunk_bytes, total;
+  uint8_t* sel;
+  int32_t *tmp_i, *send1, *recv1, *send2, *recv2;
+  float* tmp_c;
+  uint8_t* chunk;
+};
+GroupLayout group_layout(const cbv2_groups* g, const cbv2_comm* c, int32_t B, int32_t k, int32_t r, void* ws) {
+  GroupLayout L{};
+  uint8_t* base = (uint8_t*)ws;
+  size_t off = 0;
+  auto take = [&](size_t bytes) -> uint8_t* {
+    uint8_t* p = base ? base + off : nullptr;
+    off += align256(bytes);
+    return p;
+  };
+  const size_t bk = (size_t)B * k * 4;
+  L.sel_bytes = cbv2_group_topk_workspace_size(g, B, k, 1);
+  L.chunk_bytes = cbv2_group_chunks_workspace_size(B, k);
+  L.sel = take(L.sel_bytes);
+  L.tmp_i = (int32_t*)take(bk);
+  L.tmp_c = (float*)take(bk);
+  L.send1 = (int32_t*)take(2 * bk);
+  L.recv1 = (int32_t*)take(2 * bk * c->nranks);
+  L.chunk = take(L.chunk_bytes);
+  L.send2 = (int32_t*)take(2 * bk * r);
+  L.recv2 = (int32_t*)take(2 * bk * r * c->nranks);
+  L.total = off;
+  return L;
+}
+
+bool group_sizes_ok(int32_t B, int32_t k, int32_t r) { return B >= 1 && k >= 1 && r >= 1 && r <= 8; }
+
+// Everything the protocol checks itself (the local stages check the rest,
+// before their first launch and before the first collective).
+int check_group_sharded(const cbv2_groups* g, const cbv2_comm* c, int32_t B, int32_t k, int32_t r, const void* ws,
+                        size_t ws_bytes, size_t need, const float* out_scores, const int32_t* out_groups,
+                        const int32_t* out_ids, const float* out_chunk_scores) {
+  if (!g || !c) return err(CBV2_EINVAL, "null groups/comm");
+  if (!group_sizes_ok(B, k, r)) return err(CBV2_EINVAL, "bad sizes (B %d, k %d, r %d; r in [1, 8])", B, k, r);
+  if (!out_scores || !out_groups || !out_ids || !out_chunk_scores) return err(CBV2_EINVAL, "null outputs");
+  if ((int64_t)c->nranks * k > kGroupMergeMax)
+    return err(CBV2_EUNSUPPORTED, "the sharded grouped search takes G k <= %lld (got %d x %d)",
+               (long long)kGroupMergeMax, c->nranks, k);
+  if (!ws || ws_bytes < need || ((uintptr_t)ws & 15u))
+    return err(CBV2_EINVAL, "workspace too small or misaligned (%zu bytes needed)", need);
+  return CBV2_OK;
+}
+
+// The protocol over this rank's score matrix (arguments checked).
+int group_protocol(const cbv2_groups* g, cbv2_comm* c, const float* scores, int64_t ld, int32_t B, int32_t k,
+                   int32_t r, void* ws, float* out_scores, int32_t* out_groups, int32_t* out_ids,
+                   float* out_chunk_scores, hipStream_t st) {
+  const GroupLayout L = group_layout(g, c, B, k, r, ws);
+  const size_t bk = (size_t)B * k, bkr = bk * r;
+  // round 1: the local top-k groups straight into the send block
+  int rc = cbv2_group_topk_rows(g, scores, ld, B, k, 1, L.sel, L.sel_bytes, (float*)L.send1, L.send1 + bk, L.tmp_i,
+                                L.tmp_c, st);
+  if (rc) return rc;
+  rc = nccl_check(c, c->all_gather(L.send1, L.recv1, 2 * bk, kNcclInt32, c->nccl, st), "ncclAllGather");
+  if (rc) return rc;
+  ++c->gathers;
+  if ((rc = cbv2_merge_group_topk((const float*)L.recv1, L.recv1 + bk, c->nranks, B, k, (int64_t)(2 * bk), out_scores,
+                                  out_groups, st)))
+    return rc;
+  // round 2: this rank's best r chunks of the selected groups
+  rc = cbv2_group_chunks_rows(g, scores, ld, B, k, r, out_groups, L.chunk, L.chunk_bytes, L.send2,
+                              (float*)(L.send2 + bkr), st);
+  if (rc) return rc;
+  rc = nccl_check(c, c->all_gather(L.send2, L.recv2, 2 * bkr, kNcclInt32, c->nccl, st), "ncclAllGather");
+  if (rc) return rc;
+  ++c->gathers;
+  if ((rc = cbv2_merge_group_chunks(L.recv2, (const float*)(L.recv2 + bkr), c->nranks, B, k, r, (int64_t)(2 * bkr),
+                                    out_ids, out_chunk_scores, st)))
+    return rc;
+  return cbv2_group_lead_scores(out_chunk_scores, B, k, r, out_scores, st);
+}
+}  // namespace
+
+size_t cbv2_group_sharded_workspace_bytes(const cbv2_groups* g, const cbv2_comm* c, int32_t B, int32_t k, int32_t r) {
+  if (!g || !c || !group_sizes_ok(B, k, r)) return 0;
+  return group_layout(g, c, B, k, r, nullptr).total;
+}
+
+int cbv2_group_topk_sharded(const cbv2_groups* g, cbv2_comm* c, const float* scores, int64_t ld, int32_t B, int32_t k,
+                            int32_t r, void* workspace, size_t workspace_bytes, float* out_scores,
+                            int32_t* out_groups, int32_t* out_ids, float* out_chunk_scores, void* stream) {
+  const size_t need = cbv2_group_sharded_workspace_bytes(g, c, B, k, r);
+  if (int rc = check_group_sharded(g, c, B, k, r, workspace, workspace_bytes, need, out_scores, out_groups, out_ids,
+                                   out_chunk_scores))
+    return rc;
+  return group_protocol(g, c, scores, ld, B, k, r, workspace, out_scores, out_groups, out_ids, out_chunk_scores,
+                        (hipStream_t)stream);
+}
+
+size_t cbv2_search_grouped_sharded_workspace_size(const cbv2_index* ix, const cbv2_groups* g, const cbv2_comm* c,
+                                                  int32_t B, int32_t lq, int32_t k, int32_t r, int32_t scorer) {
+  if (!ix || !g || !c || lq < 1 || !group_sizes_ok(B, k, r)) return 0;
+  return align256(cbv2_grouped_scores_bytes(ix, B, lq, scorer)) + group_layout(g, c, B, k, r, nullptr).total;
+}
+
+int cbv2_search_grouped_sharded(cbv2_index* ix, const cbv2_groups* g, cbv2_comm* c, int32_t scorer, const void* Q,
+                                int32_t q_dtype, int32_t B, int32_t lq, int32_t k, int32_t r, void* workspace,
+                                size_t workspace_bytes, float* out_scores, int32_t* out_groups, int32_t* out_ids,
+                                float* out_chunk_scores, void* stream) {
+  if (!ix) return err(CBV2_EINVAL, "null index");
+  if (lq < 1) return err(CBV2_EINVAL, "lq must be >= 1 (got %d)", lq);
+  const size_t need = cbv2_search_grouped_sharded_workspace_size(ix, g, c, B, lq, k, r, scorer);
+  if (int rc = check_group_sharded(g, c, B, k, r, workspace, workspace_bytes, need, out_scores, out_groups, out_ids,
+                                   out_chunk_scores))
+    return rc;
+  const size_t score_bytes = align256(cbv2_grouped_scores_bytes(ix, B, lq, scorer));
+  float* S = nullptr;
+  int64_t ld = 0;
+  // (checks the queries, the scorer and that the groups are this index's before its first launch)
+  if (int rc = cbv2_grouped_scores(ix, g, scorer, Q, q_dtype, B, lq, workspace, score_bytes, &S, &ld, stream)) return rc;
+  return group_protocol(g, c, S, ld, B, k, r, (uint8_t*)workspace + score_bytes, out_scores, out_groups, out_ids,
+                        out_chunk_scores, (hipStream_t)stream);
 }
 
 int cbv2_comm_stats(const cbv2_comm* c, int64_t* out2) {

@@ -108,6 +108,84 @@ class _DeviceOps:
         from .index import select_topk
         return select_topk(scores, k, ids=ids)
 
+    # the sharded grouped search: the two local stages over a score matrix, the two merges
+    @staticmethod
+    def group_topk(scores: torch.Tensor, k: int, groups):
+        from .index import group_topk_rows
+        s, g, _, _ = group_topk_rows(scores, k, groups, 1)
+        return s, g
+
+    @staticmethod
+    def group_chunks(scores: torch.Tensor, sel_groups: torch.Tensor, groups, per_group: int):
+        from .index import group_chunks_rows
+        return group_chunks_rows(scores, sel_groups, groups, per_group)
+
+    @staticmethod
+    def merge_group_topk(S: torch.Tensor, Gr: torch.Tensor, k: int):
+        from .index import merge_group_topk
+        return merge_group_topk(S, Gr, k)
+
+    @staticmethod
+    def merge_group_chunks(I: torch.Tensor, C: torch.Tensor):
+        from .index import merge_group_chunks
+        return merge_group_chunks(I, C)
+
+
+def _f2u(x: np.ndarray) -> np.ndarray:
+    """The order-preserving uint32 key of a float32 (the kernels' f2u)."""
+    u = np.ascontiguousarray(x, dtype=np.float32).view(np.uint32)
+    return np.where(u >> 31 != 0, ~u, u | np.uint32(0x80000000)).astype(np.uint32)
+
+
+def _u2f(k: np.ndarray) -> np.ndarray:
+    k = np.asarray(k, dtype=np.uint32)
+    return np.ascontiguousarray(np.where(k >> 31 != 0, k & np.uint32(0x7FFFFFFF), ~k).astype(np.uint32)).view(
+        np.float32)
+
+
+def merge_group_topk_host(S: np.ndarray, Gr: np.ndarray, k: int):
+    """numpy twin of cbv2_merge_group_topk (the CPU ops of the gloo path): S f32
+    / Gr int32 [G, B, k] -> ([B, k] f32, [B, k] int32), bit for bit."""
+    S, Gr = np.asarray(S, np.float32), np.asarray(Gr, np.int32)
+    G, B, kk = S.shape
+    out_s = np.full((B, k), -np.inf, np.float32)
+    out_g = np.full((B, k), -1, np.int32)
+    keys = _f2u(S)
+    for b in range(B):
+        g, s = Gr[:, b].reshape(-1), keys[:, b].reshape(-1)
+        g, s = g[g >= 0], s[g >= 0]
+        if g.size == 0:
+            continue
+        # (group ascending, score descending): the first entry of a group's run is its maximum
+        order = np.lexsort((~s, g))
+        g, s = g[order], s[order]
+        head = np.concatenate([[True], g[1:] != g[:-1]])
+        g, s = g[head], s[head]
+        rank = (s.astype(np.uint64) << np.uint64(32)) | (~g.astype(np.uint32)).astype(np.uint64)
+        top = np.argsort(rank)[::-1][:k]
+        out_s[b, : top.size] = _u2f(s[top])
+        out_g[b, : top.size] = g[top]
+    return out_s, out_g
+
+
+def merge_group_chunks_host(I: np.ndarray, C: np.ndarray):
+    """numpy twin of cbv2_merge_group_chunks: I int32 / C f32 [G, B, k, r] ->
+    [B, k, r], bit for bit."""
+    I, C = np.asarray(I, np.int32), np.asarray(C, np.float32)
+    G, B, k, r = I.shape
+    out_i = np.full((B, k, r), -1, np.int32)
+    out_c = np.full((B, k, r), -np.inf, np.float32)
+    keys = _f2u(C)
+    for b in range(B):
+        for j in range(k):
+            i, s = I[:, b, j].reshape(-1), keys[:, b, j].reshape(-1)
+            i, s = i[i >= 0], s[i >= 0]
+            rank = np.unique((s.astype(np.uint64) << np.uint64(32)) | (~i.astype(np.uint32)).astype(np.uint64))
+            top = rank[::-1][:r]
+            out_i[b, j, : top.size] = (~(top & np.uint64(0xFFFFFFFF)).astype(np.uint32)).astype(np.int32)
+            out_c[b, j, : top.size] = _u2f((top >> np.uint64(32)).astype(np.uint32))
+    return out_i, out_c
+
 
 class _PinnedStage:
     """Host -> device uploads that do not block the host.
@@ -259,6 +337,54 @@ class NativeExchange:
             return out_s, out_i, out_li, _NativePool(ws, B, int(k), kb)
         return out_s, out_i, out_li
 
+    def _group_outputs(self, B: int, k: int, r: int):
+        return (torch.empty((B, k), dtype=torch.float32, device=self.dev),
+                torch.empty((B, k), dtype=torch.int32, device=self.dev),
+                torch.empty((B, k, r), dtype=torch.int32, device=self.dev),
+                torch.empty((B, k, r), dtype=torch.float32, device=self.dev))
+
+    def group_topk_rows(self, scores: torch.Tensor, k: int, groups, per_group: int = 1):
+        """cbv2_group_topk_sharded: the sharded grouped selection over this
+        rank's [B, n_local] score matrix (two all-gathers)."""
+        from .index import _stream_ptr
+        L = self._lib.lib()
+        k, r = int(k), int(per_group)
+        scores = scores.to(device=self.dev, dtype=torch.float32)
+        if scores.dim() == 1:
+            scores = scores.unsqueeze(0)
+        if scores.stride(1) != 1:
+            scores = scores.contiguous()
+        B, n = int(scores.shape[0]), int(scores.shape[1])
+        if n != groups.index.n:
+            raise ValueError(f"scores must be [B, {groups.index.n}] (got {tuple(scores.shape)})")
+        need = int(L.cbv2_group_sharded_workspace_bytes(groups._h, self._h, B, k, r))
+        ws = torch.empty((max(need, 16),), dtype=torch.uint8, device=self.dev)
+        outs = self._group_outputs(B, k, max(r, 1))
+        self._lib.check(L.cbv2_group_topk_sharded(groups._h, self._h, scores.data_ptr(),
+                                                  scores.stride(0) if B > 1 else max(n, 1), B, k, r, ws.data_ptr(),
+                                                  ws.numel(), *(o.data_ptr() for o in outs), _stream_ptr(self.dev)))
+        return outs
+
+    def search_grouped(self, Q: torch.Tensor, k: int, groups, per_group: int = 1, scorer: str = "maxsim"):
+        """cbv2_search_grouped_sharded (two all-gathers): what
+        ``ColbertIndex.search_grouped`` returns for the whole corpus."""
+        from .index import _stream_ptr
+        if self.index._query_blocks(Q, scorer) is not None:   # long queries: summed block scores, the rows form
+            return self.group_topk_rows(self.index.score(Q, scorer), k, groups, per_group)
+        L = self._lib.lib()
+        k, r = int(k), int(per_group)
+        sid = self.index._scorer(scorer)
+        _keep, qptr, qdt, B, lq = self.index._prep_query(Q, scorer)
+        need = int(L.cbv2_search_grouped_sharded_workspace_size(self.index._h, groups._h, self._h, B, lq, k, r, sid))
+        ws = self._ws[2]
+        if ws is None or ws.numel() < need:
+            ws = self._ws[2] = torch.empty((max(need, 16),), dtype=torch.uint8, device=self.dev)
+        outs = self._group_outputs(B, k, max(r, 1))
+        self._lib.check(L.cbv2_search_grouped_sharded(self.index._h, groups._h, self._h, sid, qptr, qdt, B, lq, k, r,
+                                                      ws.data_ptr(), ws.numel(), *(o.data_ptr() for o in outs),
+                                                      _stream_ptr(self.dev)))
+        return outs
+
     def rerank(self, Q: torch.Tensor, cand: torch.Tensor, k: int, pool=None, misses: torch.Tensor = None):
         """Stage 3.  pool (from ``search(..., return_pool=True)`` of the batch
         whose lists the candidates were fused from): the scores are looked up
@@ -324,7 +450,9 @@ class ShardedSearcher:
     """
 
     def __init__(self, local, group: Optional[dist.ProcessGroup] = None, ops=None, world: Optional[int] = None,
-                 native: bool = False, lexical_k: int = 100):
+                 native: bool = False, lexical_k: int = 100, comm=None):
+        """``comm``: an existing ``cbv2_comm*`` handle for the native exchange to
+        adopt (``loopback_comms``, test-only); implies ``native``."""
         self.local = local
         self.group = group
         self._stage = _PinnedStage()
@@ -333,7 +461,7 @@ class ShardedSearcher:
             world = dist.get_world_size(group) if dist.is_initialized() else 1
         self.world = world
         # native=True: the whole exchange runs inside the C ABI (NativeExchange)
-        self._nx = NativeExchange(local, group, lexical_k) if native else None
+        self._nx = NativeExchange(local, group, lexical_k, comm=comm) if native or comm is not None else None
         self._coll = None          # collective timing record (time_collectives)
         self.last_pool_misses = None   # the last pooled rerank's count of candidates in no list (tensor)
 
@@ -465,6 +593,54 @@ class ShardedSearcher:
         G, B = parts.shape[0], parts.shape[1]
         flat = parts.permute(1, 0, 2, 3).reshape(B, -1, 2)
         return _TorchPool(flat[..., 1].contiguous(), flat[..., 0].contiguous().view(torch.float32))
+
+    def search_grouped(self, Q: torch.Tensor, k: int, groups, per_group: int = 1, scorer: str = "maxsim"):
+        """The top-k GROUPS (documents) of the whole corpus, each with its best
+        ``per_group`` chunks: ``ColbertIndex.search_grouped``'s four tensors,
+        bit for bit those of the unsharded search and identical on every rank.
+
+        ``groups``: this rank's ``DocGroups`` built from ``group_of`` (its slice
+        of the corpus-wide assignment) with the corpus-wide ``G`` -- all ranks
+        share one group index space, and a group may have chunks on any number
+        of ranks.  The ``keys`` form numbers groups per shard and is refused.
+        Two collectives: the local top-k groups are gathered
+        and merged (maximum per group, then top-k), then every rank's best
+        chunks of the selected groups are gathered and merged per slot.  The
+        local stages run over this rank's full score matrix (``score()``; on a
+        faithful shard the full faithful scan: the certified band is not used
+        under sharding); ``native=True`` runs the whole protocol inside the C
+        ABI (cbv2_search_grouped_sharded)."""
+        if getattr(groups, "keyed", False):
+            raise ValueError("a sharded grouped search needs DocGroups built from group_of with the corpus-wide G: "
+                             "groups(keys=...) numbers the groups of each shard on its own")
+        k, r = int(k), int(per_group)
+        if k < 1 or not 1 <= r <= 8:
+            raise ValueError(f"k must be >= 1 and per_group in [1, 8] (got k={k}, per_group={r})")
+        if self._nx is not None:
+            return self._nx.search_grouped(Q, k, groups, r, scorer)
+        S = self.local.score(Q, scorer)
+        return self.group_topk_rows(S, k, groups, r)
+
+    def group_topk_rows(self, scores: torch.Tensor, k: int, groups, per_group: int = 1):
+        """The sharded grouped selection over this rank's [B, n_local] score
+        matrix (the protocol of ``search_grouped`` without the scan)."""
+        k, r = int(k), int(per_group)
+        if self._nx is not None:
+            return self._nx.group_topk_rows(scores, k, groups, r)
+        if self.world * k > 16384:     # cbv2_merge_group_topk's limit; equal on all ranks: all refuse together
+            raise ValueError(f"the sharded grouped search takes world * k <= 16384 (got {self.world} x {k})")
+        s, g = self.ops.group_topk(scores, k, groups)
+        if dist.is_initialized() and self.world > 1:
+            allp = self._all_gather(torch.stack([s.contiguous().view(torch.int32), g.to(torch.int32)], dim=-1))
+        else:
+            allp = torch.stack([s.contiguous().view(torch.int32), g.to(torch.int32)], dim=-1).unsqueeze(0)
+        _, sel = self.ops.merge_group_topk(allp[..., 0].contiguous().view(torch.float32), allp[..., 1].contiguous(), k)
+        ids, cs = self.ops.group_chunks(scores, sel, groups, r)
+        packed = torch.stack([ids.to(torch.int32), cs.contiguous().view(torch.int32)], dim=-1)   # [B, k, r, 2]
+        allc = self._all_gather(packed) if dist.is_initialized() and self.world > 1 else packed.unsqueeze(0)
+        out_i, out_c = self.ops.merge_group_chunks(allc[..., 0].contiguous(),
+                                                   allc[..., 1].contiguous().view(torch.float32))
+        return out_c[:, :, 0].contiguous(), sel, out_i, out_c
 
     def search_exchange(self, s: torch.Tensor, i: torch.Tensor, k: int):
         packed = torch.stack([s.contiguous().view(torch.int32), i.to(torch.int32)], dim=-1)  # [B, k, 2]

@@ -359,6 +359,10 @@ class DocGroups:
         self._h = h
         self.count = int(L.cbv2_groups_count(h))
         self.members = int((self.group_of >= 0).sum())   # chunks in some group
+        # True when ``ColbertIndex.groups(keys=...)`` numbered the groups: per
+        # shard, in order of first appearance, so the indices mean nothing on
+        # another shard (ShardedSearcher.search_grouped refuses such a handle)
+        self.keyed = False
 
     def close(self) -> None:
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -938,7 +942,9 @@ class ColbertIndex:
         if G is not None:
             raise ValueError("G goes with group_of; keys number their own groups")
         gof, labels = group_labels(keys)
-        return DocGroups(self, gof, max(len(labels), 1), labels if labels else [None])
+        out = DocGroups(self, gof, max(len(labels), 1), labels if labels else [None])
+        out.keyed = True
+        return out
 
     def _check_groups(self, groups: DocGroups, per_group: int) -> int:
         if not isinstance(groups, DocGroups):
@@ -1304,6 +1310,76 @@ def group_topk_rows(scores: torch.Tensor, k: int, groups: DocGroups, per_group: 
                                       ws.data_ptr(), ws.numel(), out_s.data_ptr(), out_g.data_ptr(),
                                       out_i.data_ptr(), out_c.data_ptr(), _stream_ptr(dev)))
     return out_s, out_g, out_i, out_c
+
+
+def group_chunks_rows(scores: torch.Tensor, sel_groups: torch.Tensor, groups: DocGroups, per_group: int = 1):
+    """Round 2 of the sharded grouped search on its own (cbv2_group_chunks_rows):
+    for each entry of ``sel_groups`` int32 [B, k] (group indices, -1 = padding)
+    the best ``per_group`` chunks of that group among this shard's, from a
+    [B, n] score matrix: (global chunk ids int32 [B, k, per_group], their
+    scores f32); -1 / -inf where the shard has no chunk of the group."""
+    _require_cuda(scores, "scores")
+    if not isinstance(groups, DocGroups):
+        raise TypeError("groups must be a DocGroups (ColbertIndex.groups)")
+    if not groups._h.value:
+        raise ValueError("the groups handle is closed")
+    r = int(per_group)
+    if scores.dim() == 1:
+        scores = scores.unsqueeze(0)
+    scores = scores.to(torch.float32)
+    if scores.stride(1) != 1:
+        scores = scores.contiguous()
+    B, n = scores.shape
+    if n != groups.index.n:
+        raise ValueError(f"scores must be [B, {groups.index.n}] (got {tuple(scores.shape)})")
+    dev = scores.device
+    sel = sel_groups.to(device=dev, dtype=torch.int32).contiguous()
+    if sel.dim() != 2 or sel.shape[0] != B:
+        raise ValueError(f"sel_groups must be [{B}, k] (got {tuple(sel.shape)})")
+    k = int(sel.shape[1])
+    L = _lib.lib()
+    need = int(L.cbv2_group_chunks_workspace_size(B, k))
+    ws = torch.empty((max(need, 16),), dtype=torch.uint8, device=dev)
+    out_i = torch.empty((B, k, max(r, 1)), dtype=torch.int32, device=dev)
+    out_c = torch.empty((B, k, max(r, 1)), dtype=torch.float32, device=dev)
+    _lib.check(L.cbv2_group_chunks_rows(groups._h, scores.data_ptr(), scores.stride(0) if B > 1 else max(n, 1), B, k,
+                                        r, sel.data_ptr(), ws.data_ptr(), ws.numel(), out_i.data_ptr(),
+                                        out_c.data_ptr(), _stream_ptr(dev)))
+    return out_i, out_c
+
+
+def merge_group_topk(scores: torch.Tensor, groups: torch.Tensor, k: int):
+    """Merge [G, B, k] per-shard (group score, group index) lists into the
+    global top-k groups [B, k] (cbv2_merge_group_topk): the maximum per group,
+    then score descending, group index ascending; group < 0 is padding."""
+    _require_cuda(scores, "scores")
+    scores = scores.to(torch.float32).contiguous()
+    groups = groups.to(device=scores.device, dtype=torch.int32).contiguous()
+    G, B, kk = scores.shape
+    if kk != k or groups.shape != scores.shape:
+        raise ValueError("per-shard lists must be [G, B, k], scores and groups alike")
+    out_s = torch.empty((B, k), dtype=torch.float32, device=scores.device)
+    out_g = torch.empty((B, k), dtype=torch.int32, device=scores.device)
+    _lib.check(_lib.lib().cbv2_merge_group_topk(scores.data_ptr(), groups.data_ptr(), G, B, int(k), B * int(k),
+                                                out_s.data_ptr(), out_g.data_ptr(), _stream_ptr(scores.device)))
+    return out_s, out_g
+
+
+def merge_group_chunks(ids: torch.Tensor, chunk_scores: torch.Tensor):
+    """Merge [G, B, k, r] per-shard chunk lists of the selected groups into
+    [B, k, r] (cbv2_merge_group_chunks): score descending, chunk id ascending;
+    id < 0 is padding."""
+    _require_cuda(chunk_scores, "chunk_scores")
+    cs = chunk_scores.to(torch.float32).contiguous()
+    ids = ids.to(device=cs.device, dtype=torch.int32).contiguous()
+    if cs.dim() != 4 or ids.shape != cs.shape:
+        raise ValueError("per-shard lists must be [G, B, k, r], ids and scores alike")
+    G, B, k, r = cs.shape
+    out_i = torch.empty((B, k, r), dtype=torch.int32, device=cs.device)
+    out_c = torch.empty((B, k, r), dtype=torch.float32, device=cs.device)
+    _lib.check(_lib.lib().cbv2_merge_group_chunks(ids.data_ptr(), cs.data_ptr(), G, B, k, r, B * k * r,
+                                                  out_i.data_ptr(), out_c.data_ptr(), _stream_ptr(cs.device)))
+    return out_i, out_c
 
 
 def merge_topk(scores: torch.Tensor, ids: torch.Tensor, k: int):

@@ -41,6 +41,10 @@ class JinaColBERTRetriever:
         self.model = encoder if encoder is not None else load_local_encoder(config.embedding_model, dev)
         self.corpus_embeddings: Optional[ColbertIndex] = None
         self.corpus: Optional[List[str]] = None
+        # a distributed.ShardedSearcher over this rank's shard (``corpus_embeddings``), set by the
+        # caller when the corpus is sharded over several GPUs: search_grouped then answers for
+        # the whole corpus
+        self.searcher = None
 
     @property
     def scorer(self) -> str:
@@ -225,19 +229,27 @@ class JinaColBERTRetriever:
         ``per_group`` chunks: [{'group': label, 'score', 'chunks':
         [{'document_id', 'score', 'text'}, ...]}], best first; a group's score is
         its best chunk's, and 'document_id' is the chunk id, as in ``search``.
-        ``groups``: a ``DocGroups`` (``make_groups``) or the per-chunk keys."""
+        ``groups``: a ``DocGroups`` (``make_groups``) or the per-chunk keys.
+        With a ``searcher`` (a sharded corpus) the answer covers every shard;
+        ``groups`` must then be this shard's ``DocGroups`` built from
+        ``group_of`` with the corpus-wide group count."""
         ix = self.corpus_embeddings
         if ix is None:
             raise RuntimeError("no index: call index() or load() first")
         if groups is None:
             raise ValueError("search_grouped needs groups (make_groups) or the chunks' keys")
-        grp = groups if isinstance(groups, DocGroups) else self.make_groups(groups)
-        kk = min(int(k), grp.count)
+        if self.searcher is not None:
+            if not isinstance(groups, DocGroups):
+                raise ValueError("a sharded search_grouped takes DocGroups built from group_of with the corpus-wide G")
+            grp, kk = groups, int(k)       # (other shards may hold groups this one lacks)
+        else:
+            grp = groups if isinstance(groups, DocGroups) else self.make_groups(groups)
+            kk = min(int(k), grp.count)
         if kk <= 0:
             return []
         q = self._encode_query(query)
-        scores, gidx, ids, cscores = ix.search_grouped(q.unsqueeze(0), kk, grp, per_group=per_group,
-                                                       scorer=self.scorer)
+        run = self.searcher.search_grouped if self.searcher is not None else ix.search_grouped
+        scores, gidx, ids, cscores = run(q.unsqueeze(0), kk, grp, per_group=per_group, scorer=self.scorer)
         scores, gidx, ids, cscores = scores[0].tolist(), gidx[0].tolist(), ids[0].tolist(), cscores[0].tolist()
         return [{"group": grp.labels[g], "score": float(s),
                  "chunks": [{"document_id": int(i), "score": float(c), "text": self.corpus[i] if self.corpus else None}

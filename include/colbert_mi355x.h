@@ -686,6 +686,80 @@ cbv2_search_grouped_f32(cbv2_index* index, const cbv2_groups* groups, const floa
                             float* out_scores, int32_t* out_groups, int32_t* out_ids, float* out_chunk_scores,
                             int32_t* out_status, void* stream);
 
+/* Sharded grouped search ("Across shards"): the grouped search
+ * of a corpus in contiguous shards, one rank per shard, bit for bit the
+ * unsharded cbv2_search_grouped / cbv2_group_topk_rows of the whole corpus on
+ * every rank.  All ranks share ONE group index space [0, G): each rank creates
+ * its cbv2_groups from its own slice of group_of with the same G (a group may
+ * have chunks on every rank, on some, or on none).  Two collectives per call:
+ *   round 1  each rank's local top-k groups (r = 1) -> all-gather of the
+ *            [scores B k | groups B k] blocks -> cbv2_merge_group_topk: the
+ *            maximum per group over the G lists, then the top k.  Exact: a
+ *            group of the global top-k is in the local top-k of the rank that
+ *            attains its score, and a list can only under-estimate the others.
+ *   round 2  each rank's best r chunks of the k selected groups
+ *            (cbv2_group_chunks_rows) -> all-gather of the [ids B k r | scores
+ *            B k r] blocks -> cbv2_merge_group_chunks.  Round 1's chunks do not
+ *            do: a selected group's runner-up chunk can sit on a rank where
+ *            the group is outside the local top-k.
+ *   out_scores[b][j] is then set to out_chunk_scores[b][j][0] (the same bits).
+ *  The pieces, each asynchronous, capturable and without a host round trip,
+ *  every argument checked before any launch:
+ *  - cbv2_group_chunks_rows: to round 2 what cbv2_group_topk_rows is to the
+ *    search.  sel_groups int32 [B][k]: the caller's group indices, -1 for
+ *    padding.  out_ids / out_chunk_scores [B][k][r]: the best r chunks of
+ *    each selected group among this shard's (cbv2_search_grouped's order and
+ *    padding); a padding entry, an index outside [0, G) and a group without a
+ *    member on this shard give -1 / -inf in all r slots.  The workspace, 16-B
+ *    aligned, of cbv2_group_chunks_workspace_size(B, k) = 2 r256(4 B k) bytes
+ *    (0 for B or k < 1), holds the groups' positions and a scratch copy of
+ *    their indices; its contents need not survive the call.
+ *  - cbv2_merge_group_topk: in_scores f32 / in_groups int32, rank g's [B][k]
+ *    list at g * stride elements (stride >= B k; group < 0: padding, in any
+ *    slot; lists need not be sorted).  Duplicates of a group reduce to their
+ *    maximum; out_scores / out_groups [B][k]: score descending, then group
+ *    index ascending, padded with -inf / -1.  1 <= G <= 64 and G k <= 16384
+ *    (the keys of a row are sorted in 128 KiB of LDS); beyond that
+ *    CBV2_EUNSUPPORTED and nothing is launched.
+ *  - cbv2_merge_group_chunks: in_ids int32 / in_cs f32, rank g's [B][k][r] list
+ *    at g * stride elements (stride >= B k r; id < 0: padding).  Per (b, j) the
+ *    best r of the G r chunks, score descending, then chunk id ascending; a
+ *    chunk scoring -inf keeps its id and ranks after every finite chunk;
+ *    padded with -1 / -inf.  1 <= G <= 64, 1 <= r <= 8.
+ *  The sharded calls are NOT capturable (a collective), and every rank must
+ *  make them in the same order with the same B, k, r:
+ *  - cbv2_group_topk_sharded: the protocol over a caller score matrix, row b at
+ *    scores[b * ld + i], i < n_local (ld >= n_local).
+ *  - cbv2_search_grouped_sharded: the scorer's scores of every local chunk into
+ *    a [B][n] block of the workspace, then the same protocol.  Query types,
+ *    scorers, ld values and lq <= 32: cbv2_search_grouped's.  On an fp32-
+ *    faithful shard with f32 queries the scores are cbv2_score_f32's FULL
+ *    faithful scan: the certified band of cbv2_search_grouped_f32 is NOT used
+ *    under sharding in this version (its T row and overflow gating belong to a
+ *    selection made on the shard itself); the results are the same bits.
+ *  An empty shard or one without a member sends padding and still joins both
+ *  collectives; fewer than k non-empty groups in all: -inf / -1 at the tail;
+ *  with one rank the result is cbv2_search_grouped's (the collectives still
+ *  run).  G k > 16384 is CBV2_EUNSUPPORTED before any launch or collective (G
+ *  and k are equal on all ranks: all refuse together), like every argument
+ *  error.  cbv2_comm_stats counts two all-gathers per call.  Workspaces (16-B
+ *  aligned; 0 for a null handle, B or k < 1, r outside [1, 8], lq < 1):
+ *  cbv2_group_sharded_workspace_bytes(groups, comm, B, k, r) and
+ *  cbv2_search_grouped_sharded_workspace_size(index, groups, comm, B, lq, k, r,
+ *  scorer).
+ * (Guard-band tests: tests/test_gpu_group_sharded.py.) */
+size_t cbv2_group_chunks_workspace_size(int32_t B, int32_t k);
+int
+cbv2_group_chunks_rows(const cbv2_groups* groups, const float* scores, int64_t ld, int32_t B, int32_t k, int32_t r,
+                           const int32_t* sel_groups, void* workspace, size_t workspace_bytes, int32_t* out_ids,
+                           float* out_chunk_scores, void* stream);
+int
+cbv2_merge_group_topk(const float* in_scores, const int32_t* in_groups, int32_t G, int32_t B, int32_t k,
+                          int64_t stride, float* out_scores, int32_t* out_groups, void* stream);
+int
+cbv2_merge_group_chunks(const int32_t* in_ids, const float* in_cs, int32_t G, int32_t B, int32_t k, int32_t r,
+                            int64_t stride, int32_t* out_ids, float* out_cs, void* stream);
+
 /* cbv2_rerank — JinaColBERTRetriever.rerank (local_rag_complete.py:779-800)
  * without re-encoding: the C candidate docs of each query are GATHERED from
  * the HBM index by global id (cand int32 [B][C]; ids outside this shard or < 0
@@ -1005,6 +1079,21 @@ int cbv2_rerank_sharded(cbv2_index* index, cbv2_comm* comm, const void* Q, int32
                         const int32_t* cand, int32_t C, int32_t k, void* workspace, size_t workspace_bytes,
                         float* out_scores, int32_t* out_ids, int32_t* out_pos, void* stream);
 int cbv2_comm_stats(const cbv2_comm* comm, int64_t* out2);
+/* The sharded grouped search (described with the grouped search above). */
+size_t cbv2_group_sharded_workspace_bytes(const cbv2_groups* groups, const cbv2_comm* comm, int32_t B, int32_t k,
+                                          int32_t r);
+int
+cbv2_group_topk_sharded(const cbv2_groups* groups, cbv2_comm* comm, const float* scores, int64_t ld, int32_t B,
+                            int32_t k, int32_t r, void* workspace, size_t workspace_bytes, float* out_scores,
+                            int32_t* out_groups, int32_t* out_ids, float* out_chunk_scores, void* stream);
+size_t cbv2_search_grouped_sharded_workspace_size(const cbv2_index* index, const cbv2_groups* groups,
+                                                  const cbv2_comm* comm, int32_t B, int32_t lq, int32_t k, int32_t r,
+                                                  int32_t scorer);
+int
+cbv2_search_grouped_sharded(cbv2_index* index, const cbv2_groups* groups, cbv2_comm* comm, int32_t scorer,
+                                const void* Q, int32_t q_dtype, int32_t B, int32_t lq, int32_t k, int32_t r,
+                                void* workspace, size_t workspace_bytes, float* out_scores, int32_t* out_groups,
+                                int32_t* out_ids, float* out_chunk_scores, void* stream);
 
 /* TEST-ONLY -- not for production use.  cbv2_comm_loopback_init writes
  * `nranks` (1..64) communicator handles out[0..nranks) that form ONE group
