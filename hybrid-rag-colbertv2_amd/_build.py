@@ -24,6 +24,8 @@ LIB = os.path.join(PKG, "libcolbert_mi355x.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -fno-honor-nans: lets fmaxf on MFMA results lower to bare v_max3_f32 (no
 # canonicalising v_max per operand); the path never feeds NaNs on purpose.
+# Padding rows are the one place NaNs do enter (a caller's uncleared rows under
+# the additive -inf mask): tests/test_gpu_nonfinite_padding.py pins that none reaches a score.
 # The .hip sources (the library's and the lab tools') take their kernel configs
 # as class-type template arguments: C++20.  The host .cpp files stay valid C++17.
 STD = "-std=c++20"

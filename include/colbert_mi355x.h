@@ -114,6 +114,12 @@
  *             fp32-faithful index and the native file; scales of an MXFP8
  *             index are [n][ld][2]);
  *             rows t >= doclens[i] of doc i are padding and never score.
+ *             Padding rows -- of the tokens, of the residual of an
+ *             fp32-faithful index, of the f32 source matrix of the index
+ *             split and of the mean build, and for MXFP8 their scale bytes
+ *             -- may hold ANY bit pattern, NaN and Inf encodings included (an
+ *             allocation never cleared, a 0xFF byte fill): no result depends
+ *             on them (tests/test_gpu_nonfinite_padding.py).
  *    doclens  int32 [n], 0 <= doclens[i] <= ld.
  *    Local doc i has global id  id_base + i  (contiguous shard of the corpus).
  */

@@ -35,6 +35,9 @@ byte changes a score:
            (t >= L) holds planted token 0 doubled: any read of padding raises
            the score of query qb[i].  qb favours low query indices, so a batch
            of 1, 2 or 4 queries still owns a large share of the planted rows.
+           (tests/_padding.py overwrites the padding of an encoded corpus
+           with NaN / Inf encodings instead: the reference below reads the
+           scoring rows only, so it stays what it is.)
   doclens  0, 1, 15, 16, 17, 31, 32, 33, 63, 64, 65, 127, 128 and, for ld >
            128, 129, ld - 129, ld - 128, ld - 1, ld; the rest drawn so that
            every residue mod 16 and every planted slot in [0, ld) occurs (the

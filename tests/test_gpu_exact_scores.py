@@ -94,6 +94,10 @@ class _Case:
             ix = ColbertIndex(x.to(torch.bfloat16), dl, id_base=id_base)
         return ix
 
+    def tripled(self):
+        """Three copies of the corpus in one index: a mass tie at every place."""
+        return self.build(np.tile(self.c.docs_f32(), (3, 1, 1)), np.tile(self.c.doclens, 3))
+
     def queries(self, B, lq=ex.LQ):
         q = self.Q[:B, :lq].contiguous()
         return q if self.kind == "fp32" else q.to(torch.bfloat16)
@@ -134,8 +138,9 @@ def _ids(cases):
 
 
 # ---------------------------------------------------------------------------- score
-@pytest.mark.parametrize("case", CASES, indirect=True, ids=_ids(CASES))
-def test_score_equals_exact_reference(case):
+# The sweeps take the case, so that tests/test_gpu_nonfinite_padding.py plays them on indexes whose padding rows
+# hold NaN / Inf encodings.
+def sweep_score(case):
     for B in _score_batches(case.kind, case.ld):
         for dense in ((0, 1) if B <= 4 else (0,)):
             for split in ((1, 0) if case.kind == "fp32" else (1,)):
@@ -144,13 +149,22 @@ def test_score_equals_exact_reference(case):
                 case.check(got, case.want(B), f"score (dense docs {dense}, rescore split {split})", B)
 
 
-@pytest.mark.parametrize("case", CASES, indirect=True, ids=_ids(CASES))
-def test_every_query_length_equals_exact_reference(case):
+def sweep_query_lengths(case):
     for B, dense, split in _sweep_batches(case.kind, case.ld):
         case.options(dense, split)
         for lq in range(1, ex.LQ + 1):
             got = case.ix.score(case.queries(B, lq))
             case.check(got, case.want(B, lq), f"score (dense docs {dense}, rescore split {split})", B, lq)
+
+
+@pytest.mark.parametrize("case", CASES, indirect=True, ids=_ids(CASES))
+def test_score_equals_exact_reference(case):
+    sweep_score(case)
+
+
+@pytest.mark.parametrize("case", CASES, indirect=True, ids=_ids(CASES))
+def test_every_query_length_equals_exact_reference(case):
+    sweep_query_lengths(case)
 
 
 SMALL = [(kind, 128) for kind in ex.KINDS]
@@ -202,8 +216,7 @@ def _topk(ref_rows, k):
 FP32 = [("fp32", ld) for ld in LDS]
 
 
-@pytest.mark.parametrize("case", FP32, indirect=True, ids=_ids(FP32))
-def test_faithful_search_returns_reference_bits(case):
+def sweep_faithful_search(case):
     c, ix, dev = case.c, case.ix, case.dev
     k = 10
     for split in (1, 0):
@@ -215,7 +228,7 @@ def test_faithful_search_returns_reference_bits(case):
             assert torch.equal(i.cpu(), torch.from_numpy(wi).to(torch.int32)), (case.ld, B, split)
             case.check(s, torch.from_numpy(ws).to(dev), f"search_f32 (rescore split {split})", B, docs=i)
     # forced fallback: three copies of the corpus tie at the k-th place, so every band holds >= 12 > cap = 10
-    ix3 = case.build(np.tile(c.docs_f32(), (3, 1, 1)), np.tile(c.doclens, 3))
+    ix3 = case.tripled()
     for split in (1, 0):
         ix3.set_option(_lib.OPT_RESCORE_SPLIT, split)
         for B in (1, 9):
@@ -226,6 +239,11 @@ def test_faithful_search_returns_reference_bits(case):
             case.check(s, torch.from_numpy(ws).to(dev), f"search_f32 fallback (rescore split {split})", B,
                        docs=i % c.N)
     ix3.close()
+
+
+@pytest.mark.parametrize("case", FP32, indirect=True, ids=_ids(FP32))
+def test_faithful_search_returns_reference_bits(case):
+    sweep_faithful_search(case)
 
 
 def _candidates(c, B, C, seed, dev):
@@ -254,11 +272,14 @@ def _check_select(case, out, want_raw, cand, k, what, B):
     case.check(s, torch.from_numpy(ws).to(case.dev), what, B, docs=i)
 
 
-@pytest.mark.parametrize("case", FP32, indirect=True, ids=_ids(FP32))
-def test_faithful_rerank_returns_reference_bits(case):
+def rerank_shapes(case):
+    return ((3, 60), (40, 60)) + (((3, 1100),) if case.ld == 128 else ())
+
+
+def sweep_faithful_rerank(case, shapes=None):
     for split in (1, 0):
         case.options(0, split)
-        for B, C in ((3, 60), (40, 60)) + (((3, 1100),) if case.ld == 128 else ()):
+        for B, C in shapes or rerank_shapes(case):
             cand = _candidates(case.c, B, C, 100 * B + C, case.dev)
             want = _want_rerank(case, cand, B)
             Q = case.queries(B)
@@ -266,6 +287,11 @@ def test_faithful_rerank_returns_reference_bits(case):
                        docs=cand)
             _check_select(case, case.ix.rerank(Q, cand, 10), want, cand, 10,
                           f"rerank_f32 k=10 (C {C}, rescore split {split})", B)
+
+
+@pytest.mark.parametrize("case", FP32, indirect=True, ids=_ids(FP32))
+def test_faithful_rerank_returns_reference_bits(case):
+    sweep_faithful_rerank(case)
 
 
 # ---------------------------------------------------------------------------- bf16 / MXFP8 rerank
@@ -290,14 +316,18 @@ def _rerank_call(ix, Q, cand, k, with_ws):
 RERANK = [(kind, ld) for kind in ("bf16", "mxfp8") for ld in LDS]
 
 
-@pytest.mark.parametrize("case", RERANK, indirect=True, ids=_ids(RERANK))
-def test_rerank_returns_reference_bits(case):
-    for B, C in ((3, 60), (40, 60)) + (((3, 1100),) if case.ld == 128 else ()):
+def sweep_rerank(case, shapes=None):
+    for B, C in shapes or rerank_shapes(case):
         cand = _candidates(case.c, B, C, 100 * B + C, case.dev)
         want = _want_rerank(case, cand, B)
         Q = case.queries(B)
         for with_ws in (False, True):
             what = f"rerank (C {C}, {'with' if with_ws else 'no'} workspace)"
             case.check(_rerank_call(case.ix, Q, cand, 0, with_ws), want, what + " raw", B, docs=cand)
-            k = 60 if C == 60 else 20                     # k > 0: the select kernels / one workgroup per query
+            k = C if C <= 60 else 20                      # k > 0: the select kernels / one workgroup per query
             _check_select(case, _rerank_call(case.ix, Q, cand, k, with_ws), want, cand, k, what + f" k={k}", B)
+
+
+@pytest.mark.parametrize("case", RERANK, indirect=True, ids=_ids(RERANK))
+def test_rerank_returns_reference_bits(case):
+    sweep_rerank(case)

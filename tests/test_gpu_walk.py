@@ -53,6 +53,7 @@ import pytest
 import torch
 
 import _exact as ex
+import _padding as pad
 import _walk as wk
 import _walk_seeds as ws
 from hybrid_rag_colbertv2_amd import _lib
@@ -78,9 +79,12 @@ REGRESSIONS = tuple(
 
 
 class PoolDev:
-    """A pool on the device, laid out as its index kind stores it, for gathers."""
+    """A pool on the device, laid out as its index kind stores it, for gathers.
+    ``padding`` ("nan" / "inf", tests/_padding.py): the padding rows of the
+    device arrays are overwritten once, after construction; the bounds stay
+    those of the clean split."""
 
-    def __init__(self, pool, dev):
+    def __init__(self, pool, dev, padding=None):
         c = pool.corpus
         self.Q = torch.from_numpy(c.queries_f32()).to(dev)                   # [B, 32, 128] f32
         x = torch.from_numpy(c.docs_f32()).to(dev)
@@ -95,6 +99,8 @@ class PoolDev:
             self.tokens, self.extra = quantize_mxfp8(x)
         else:
             self.tokens, self.extra = x.to(torch.bfloat16), None
+        if padding is not None:
+            self.tokens, self.extra = pad.poison(pool.kind, self.tokens, self.extra, self.doclens, padding)
         torch.cuda.synchronize()
 
     def index(self, sel, id_base):
@@ -110,10 +116,10 @@ class PoolDev:
 _pool_devs = {}
 
 
-def pool_dev(kind, ld, dev):
-    if (kind, ld) not in _pool_devs:
-        _pool_devs[kind, ld] = PoolDev(wk.exact_pool(kind, ld), dev)
-    return _pool_devs[kind, ld]
+def pool_dev(kind, ld, dev, padding=None):
+    if (kind, ld, padding) not in _pool_devs:
+        _pool_devs[kind, ld, padding] = PoolDev(wk.exact_pool(kind, ld), dev, padding)
+    return _pool_devs[kind, ld, padding]
 
 
 class Buffers:
@@ -133,17 +139,24 @@ class Buffers:
 
 
 class Gpu:
-    """Plays a walk's steps through the C ABI."""
+    """Plays a walk's steps through the C ABI.  ``padding``: on a pool whose
+    padding rows hold that mode's non-finite values, and with the query buffer
+    past each step's B * lq rows filled with them (tests/_padding.query_tail),
+    so that a kernel reading a query row too many meets a NaN and not the
+    previous step's finite queries."""
 
-    def __init__(self, dev, bufs, repoison=False, zeroed=False):
-        self.dev, self.bufs, self.repoison, self.zeroed = dev, bufs, repoison, zeroed
+    def __init__(self, dev, bufs, repoison=False, zeroed=False, padding=None):
+        self.dev, self.bufs, self.repoison, self.zeroed, self.padding = dev, bufs, repoison, zeroed, padding
         self.L = _lib.lib()
         self.ix = None
+        self.qtail = None
 
     # ----- the player's interface
     def start(self, w, pool, opts=None):
         self.w, self.pool = w, pool
-        self.pd = pool_dev(w.kind, w.ld, self.dev)
+        self.pd = pool_dev(w.kind, w.ld, self.dev, self.padding)
+        if self.padding is not None:
+            self.qtail = torch.from_numpy(pad.query_tail(w.kind, self.padding, self.bufs.q.numel())).to(self.dev)
         self.ix = self.pd.index(w.sel, w.id_base)
         self.h = self.ix._h
         self.faithful = w.kind == "fp32"
@@ -192,7 +205,7 @@ class Gpu:
         """The failing step alone on a fresh index and a fresh zeroed workspace."""
         torch.cuda.synchronize()
         fresh = Gpu(self.dev, Buffers(self.dev, self.bufs.ws[0].numel(), self.bufs.q.numel(), self.bufs.host.numel()),
-                    zeroed=True)
+                    zeroed=True, padding=self.padding)
         try:
             fresh.start(self.w, self.pool, opts=step["opts"])
             msg = wk.compare(fresh, fresh.call(i, step), want)
@@ -236,6 +249,9 @@ class Gpu:
             self.keep.append(Q)
             _lib.check(self.L.cbv2_quantize_mxfp8(Q.data_ptr(), _lib.DTYPE_F32, n_rows, qb.data_ptr(),
                                                   qb.data_ptr() + n_rows * 128, _stream_ptr(self.dev)))
+        if self.qtail is not None:
+            used = B * lq * {"fp32": 512, "bf16": 256, "mxfp8": 130}[self.w.kind]
+            qb[used:].copy_(self.qtail[used:])
         return qb.data_ptr()
 
     # ----- the call
@@ -442,12 +458,13 @@ def _chosen():
     return [(p[0], int(p[1]), int(p[2]), len(p) > 3 and p[3] == "large") for p in names] or None
 
 
-def _play(dev, keys, ws_bytes):
+def _play(dev, keys, ws_bytes, padding=None):
     t0 = time.perf_counter()
     steps = 0
     for j, key in enumerate(keys):
         w = wk.generate(*key)
-        wk.play(w, wk.exact_pool(w.kind, w.ld), Gpu(dev, _buffers(dev, ws_bytes), repoison=j % 4 == 3))
+        wk.play(w, wk.exact_pool(w.kind, w.ld),
+                Gpu(dev, _buffers(dev, ws_bytes), repoison=j % 4 == 3, padding=padding))
         steps += len(w.steps)
     print(f"{len(keys)} walks, {steps} steps in {time.perf_counter() - t0:.2f} s")
 
